@@ -16,9 +16,15 @@ as "per_step_launch".  The timed region is bracketed by a barrier + synchronize 
 sides (timed_window: the closing barrier follows the rank's clock read); the per-GPU episode
 summaries are all-gathered (RCCL) inside it, and `value` uses the max over ranks.
 
-Run:  python bench.py [--gpus N --steps K --warmup W]
+Run:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
       N>1 starts N ranks itself (child processes joining a TCPStore this process hosts on
       127.0.0.1); under an external torchrun (WORLD_SIZE set) it runs as the given rank.
+
+A plain run does what the headline needs and no more: set-up, warmup, the timed window, the
+result line.  --dump-outputs DIR also writes what the window's last step computed (dump_outputs).
+--full adds everything else after the window: the dominant kernel's duration and the roofline
+block, the cold-actions window, the secondary lines (per_step_launch, rollout, render, c3, wide,
+planner, bayes) and the CPU baseline; the --no-* options pick among those.
 """
 from __future__ import annotations
 
@@ -632,6 +638,46 @@ def timed_window(launches, gather, sync, barrier, clock=time.perf_counter):
     return t1 - t0, g
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # of float32 per-env output; the files stay well under 64 MB in all
+
+
+def dump_outputs(path: str, eb, traj, ex_all, coll_all, n: int, totals) -> dict:
+    """--dump-outputs DIR: what a caller of the timed path holds after its last step, as float32 /
+    float64 .npy files, for comparing two builds output for output (the inputs are functions of
+    the arguments alone: the reset state and the counter-RNG action streams).
+
+      env_index.npy   [m]            f64  the envs dumped: all of them while their float32 output
+                                          fits DUMP_BUDGET_BYTES, else a sorted sample drawn
+                                          without replacement by numpy RandomState(0)
+      state.npy       [planes, m]    f32  the last step's state bytes of those envs
+      exec_actions.npy [A, m]        f32  the last step's executed actions
+      collisions.npy  [m]            f32  the last step's collision masks
+      episode_totals.npy [OC_NSTATS] f64  the window's statistics totals over every env (the
+                                          in-launch fold the summary all-gather carries)
+
+    `traj`, `ex_all`, `coll_all` are the last launch's output set, `n` its number of steps."""
+    import numpy as np
+    P, A, NP, B = eb.pitch, eb.A, eb.layout.num_planes, eb.B
+    m = min(B, DUMP_BUDGET_BYTES // (4 * (NP + A + 1)))
+    idx = np.arange(B) if m == B else np.sort(np.random.RandomState(0).choice(B, m, replace=False))
+    sel = torch.from_numpy(idx).to(traj.device)
+
+    def last(buf, rows):  # step n-1 of an n x [rows][pitch] output, the chosen envs, as float32
+        return buf[(n - 1) * rows * P:n * rows * P].view(rows, P).index_select(1, sel).cpu().numpy().astype(np.float32)
+
+    arrays = {
+        "env_index": idx.astype(np.float64),
+        "state": last(traj, NP),
+        "exec_actions": last(ex_all, A),
+        "collisions": last(coll_all, 1)[0],
+        "episode_totals": totals.cpu().numpy().astype(np.float64),
+    }
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "envs": int(m), "of": int(B), "bytes": int(sum(a.nbytes for a in arrays.values()))}
+
+
 class WindowLog:
     """--window-log PATH: host timestamps of the timed windows, to lay them beside a rocprofv3
     kernel trace of the same run (tools/window_split.py itemises the window's fixed cost:
@@ -683,7 +729,7 @@ def cpu_baseline_line(args, world: int, batch: int):
     nproc there counts every core of the host) divided among the job's ranks.  At N = 1 the same
     sample on nproc threads is reported beside it, labelled oversubscribed when nproc exceeds
     the share.  The sample is one rank's shard (`batch` envs), the workload one GPU runs."""
-    if args.no_cpu_baseline:
+    if not args.full or args.no_cpu_baseline:
         return None
     hc = host_cores()
     nproc, share = hc["limits"]["nproc"], max(1, hc["threads"] // max(1, world))
@@ -778,6 +824,13 @@ def main() -> int:
     ap.add_argument("--batch", type=int, default=1 << 20, help="envs per GPU")
     ap.add_argument("--max-T", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed window also measure everything beside the headline: the kernel's duration "
+                         "and the roofline block, the cold-actions window, the secondary lines and the CPU baseline "
+                         "(the --no-* options below pick among them)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed window's last step computed to DIR/<name>.npy (dump_outputs; at "
+                         "--gpus N rank 0's shard)")
     ap.add_argument("--steps-per-launch", type=int, default=100, help="oc_step_n launch length (headline)")
     ap.add_argument("--min-warmup-ms", type=float, default=50.0, help="repeat the untimed warmup for at least this long")
     ap.add_argument("--kernel-replay-ms", type=float, default=20.0,
@@ -954,53 +1007,53 @@ def main() -> int:
     # -------------------------------------------------------------------------------------------
     elapsed_max = ocdist.max_over_ranks(elapsed, dev)
     summary = ocdist.summarize(gathered)
+    dumped = None
+    if args.dump_outputs is not None and rank == 0:  # before anything below runs the launches again
+        n_last = segs[-1][1]
+        dumped = dump_outputs(args.dump_outputs, eb, *outs[(len(segs) - 1) % n_sets], n_last, totals)
 
-    # Dominant kernel: oc_step_n_kernel.  Its mean launch duration is measured right after the
-    # timed region with HIP events on its launch stream around replays of the timed launches
-    # (same shapes, buffers and in-launch statistics fold), so the GPU queue never drains
-    # between launches and the events bracket kernel time only.  Events inside the timed region
-    # itself would add their own record cost (~4 us, tools/window_probe.py) to a window of one
-    # ~90 us launch, and the first event would also time the host's launch call.  A one-launch
-    # window is replayed back to back (each replay follows an identical launch, as the window
-    # follows its warmup).  A window of several launches is replayed each time after the warmup's
-    # launches, as in the timed region: back to back, its launches would alternate and stream
-    # every launch's actions from HBM, while in the window the first launch reads the actions
-    # the warmup left in the Infinity Cache (0.57 vs 0.44 ms per 100-step launch,
-    # profiles/r02/outalias_ab.log).
-    reps = max(1, int(math.ceil(args.kernel_replay_ms / max(1e-3, elapsed * 1e3))))
-    if len(timed) == 1:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-        for _ in range(reps):
-            timed[0]()
-        ev1.record()
-        torch.cuda.synchronize()
-        kern_total_ms = ev0.elapsed_time(ev1)
-    else:
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
-        for e0, e1 in evs:
-            for f in warm:
-                f()
-            e0.record()
-            for f in timed:
-                f()
-            e1.record()
-        torch.cuda.synchronize()
-        kern_total_ms = sum(e0.elapsed_time(e1) for e0, e1 in evs)
-    kern_ms = ocdist.max_over_ranks(kern_total_ms / (reps * len(segs)) * 1e-3, dev) * 1e3
-    # the same window with its actions evicted from the Infinity Cache (1 GiB written between)
-    flush = torch.empty(1 << 30, dtype=torch.uint8, device=dev)
-    flush.fill_(1)
-    stats.zero_()
-    del flush
-    cold, _ = timed_window(wlog.wrap(win_launches), win_gather, sync, ocdist.barrier, clock=wlog.clock("cold"))
-    cold_max = ocdist.max_over_ranks(cold, dev)
+    if args.full:
+        # Dominant kernel: oc_step_n_kernel.  Its mean launch duration is measured right after the
+        # timed region with HIP events on its launch stream around replays of the timed launches
+        # (same shapes, buffers and in-launch statistics fold), so the GPU queue never drains
+        # between launches and the events bracket kernel time only.  Events inside the timed region
+        # itself would add their own record cost (~4 us, tools/window_probe.py) to a window of one
+        # ~90 us launch, and the first event would also time the host's launch call.  A one-launch
+        # window is replayed back to back (each replay follows an identical launch, as the window
+        # follows its warmup).  A window of several launches is replayed each time after the warmup's
+        # launches, as in the timed region: back to back, its launches would alternate and stream
+        # every launch's actions from HBM, while in the window the first launch reads the actions
+        # the warmup left in the Infinity Cache (0.57 vs 0.44 ms per 100-step launch,
+        # profiles/r02/outalias_ab.log).
+        reps = max(1, int(math.ceil(args.kernel_replay_ms / max(1e-3, elapsed * 1e3))))
+        if len(timed) == 1:
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record()
+            for _ in range(reps):
+                timed[0]()
+            ev1.record()
+            torch.cuda.synchronize()
+            kern_total_ms = ev0.elapsed_time(ev1)
+        else:
+            evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+            for e0, e1 in evs:
+                for f in warm:
+                    f()
+                e0.record()
+                for f in timed:
+                    f()
+                e1.record()
+            torch.cuda.synchronize()
+            kern_total_ms = sum(e0.elapsed_time(e1) for e0, e1 in evs)
+        kern_ms = ocdist.max_over_ranks(kern_total_ms / (reps * len(segs)) * 1e-3, dev) * 1e3
+        # the same window with its actions evicted from the Infinity Cache (1 GiB written between)
+        flush = torch.empty(1 << 30, dtype=torch.uint8, device=dev)
+        flush.fill_(1)
+        stats.zero_()
+        del flush
+        cold, _ = timed_window(wlog.wrap(win_launches), win_gather, sync, ocdist.barrier, clock=wlog.clock("cold"))
+        cold_max = ocdist.max_over_ranks(cold, dev)
     wlog.dump(rank)
-    nS = eb.layout.num_planes  # state bytes per env (the u16 t counts 2)
-    bytes_launch = (nS + n_per * (nS + 2 * A + 1)) * sh.batch
-    bytes_env_step = bytes_launch / (n_per * sh.batch)
-    achieved_gbs = bytes_launch / (kern_ms * 1e-3) / 1e9
-    traffic, traffic_src = load_traffic(args.traffic_json, "oc_step_n_kernel", n_per, bytes_launch)
     value = world * sh.batch * K / elapsed_max
     line = {
         "metric": METRIC,
@@ -1033,10 +1086,20 @@ def main() -> int:
                               if window_graph is not None else "a launch call per launch, then the all-gather call"),
         },
         "open_loop": True,
-        "window_cold_actions": {
+        "episodes": summary,
+    }
+    if dumped is not None:
+        line["dumped_outputs"] = dumped
+    if args.full:
+        nS = eb.layout.num_planes  # state bytes per env (the u16 t counts 2)
+        bytes_launch = (nS + n_per * (nS + 2 * A + 1)) * sh.batch
+        bytes_env_step = bytes_launch / (n_per * sh.batch)
+        achieved_gbs = bytes_launch / (kern_ms * 1e-3) / 1e9
+        traffic, traffic_src = load_traffic(args.traffic_json, "oc_step_n_kernel", n_per, bytes_launch)
+        line["window_cold_actions"] = {
             "value": world * sh.batch * K / cold_max, "ms_per_step": cold_max * 1e3 / K,
-            "note": "the same window from the same state, its actions evicted from the Infinity Cache first"},
-        "roofline": {
+            "note": "the same window from the same state, its actions evicted from the Infinity Cache first"}
+        line["roofline"] = {
             "bound": "hbm", "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
             "frac": achieved_gbs / HBM_PEAK_GBS, "traffic": traffic,
             "frac_wall": bytes_env_step * sh.batch * K / elapsed_max / 1e9 / HBM_PEAK_GBS,
@@ -1049,24 +1112,22 @@ def main() -> int:
                                                              "HIP events around %d replays of the timed launches on "
                                                              "their stream, each after the warmup's launches (max "
                                                              "over ranks)" % reps), "traffic_source": traffic_src,
-        },
-        "episodes": summary,
-    }
-    if not args.no_per_step:
-        n_ps = K if K % 2 == 0 or K == 1 else K - 1  # even: the replayed graph ends on its start buffer
-        line["per_step_launch"] = per_step_launch(eb, acts, n_ps, W, dev, world, use_graph=not args.no_graph)
-        line["per_step_launch"]["traffic"] = load_traffic(args.traffic_json, "oc_step_kernel")[0]
-    if not args.no_rollout:
-        line["rollout"] = measure_rollout(dev, world)
-    if not args.no_render:
-        line["render"] = measure_render(dev, world, args.level, args.agents)
-    if not args.no_c3:
-        line["c3"] = measure_c3(dev, world)
-    if not args.no_wide:
-        line["wide"] = measure_wide(dev, world)
-    if not args.no_planner:
-        line["planner"] = measure_planner(dev, world)
-        line["bayes"] = measure_bayes(dev, world)
+        }
+        if not args.no_per_step:
+            n_ps = K if K % 2 == 0 or K == 1 else K - 1  # even: the replayed graph ends on its start buffer
+            line["per_step_launch"] = per_step_launch(eb, acts, n_ps, W, dev, world, use_graph=not args.no_graph)
+            line["per_step_launch"]["traffic"] = load_traffic(args.traffic_json, "oc_step_kernel")[0]
+        if not args.no_rollout:
+            line["rollout"] = measure_rollout(dev, world)
+        if not args.no_render:
+            line["render"] = measure_render(dev, world, args.level, args.agents)
+        if not args.no_c3:
+            line["c3"] = measure_c3(dev, world)
+        if not args.no_wide:
+            line["wide"] = measure_wide(dev, world)
+        if not args.no_planner:
+            line["planner"] = measure_planner(dev, world)
+            line["bayes"] = measure_bayes(dev, world)
     if rank == 0:
         line["cpu_baseline"] = cpu_baseline_line(args, world, sh.batch)
     if rank == 0:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Print the headline fields of a bench.py JSON line (used by the tools/gpu_r5*.sh scripts)."""
+"""Print the headline fields of a bench.py --full JSON line (used by the tools/gpu_r5*.sh scripts)."""
 import json
 import sys
 

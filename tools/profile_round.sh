@@ -2,14 +2,14 @@
 # Profiles for one round, run on the GPU box from the repo root:
 #   tools/profile_round.sh OUT_TAG [BENCH_ARGS...]
 # 1. rocprofv3 --kernel-trace --stats of bench.py at the driver's shape (default
-#    --steps 20 --warmup 5, secondary lines off) -> gpurun_out/OUT_TAG/bench_*
+#    --full --steps 20 --warmup 5, secondary lines off) -> OUT_TAG/bench_* in the output folder
 # 2. two --pmc passes (FETCH_SIZE, WRITE_SIZE; separate runs, no trace domains) over
 #    tools/pmc_probe.py -> gpurun_out/OUT_TAG/pmc_*, then tools/pmc_report.py -> pmc_traffic.json
 # Each GPU step has its own time limit; the script stops at the first failure.
 set -euo pipefail
 TAG=${1:?tag}
 shift || true
-ARGS=${*:---steps 20 --warmup 5 --no-per-step --no-rollout --no-render --no-c3 --no-planner --no-cpu-baseline}
+ARGS=${*:---full --steps 20 --warmup 5 --no-per-step --no-rollout --no-render --no-c3 --no-planner --no-cpu-baseline}
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
