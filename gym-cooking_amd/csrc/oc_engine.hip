@@ -17,6 +17,7 @@
 //   oc_rollout_kernel navigation-planner rollout rows (oc_rollout.h).
 //   oc_bounds_kernel  full-state subtask lower bounds + allocation feasibility (oc_subtask_bounds).
 //   oc_render_kernel  image observations.
+//   oc_observe_kernel grid feature planes + legal-move masks per env (oc_observe.h).
 //   reset / gen_actions / checksum / stats_reduce helpers.
 // All of them accumulate nothing on the host; statistics are per-block rows of no-return
 // 64-bit atomics reduced by oc_stats_reduce for the all-gather of episode summaries.
@@ -32,6 +33,7 @@
 #include <vector>
 
 #include "../../include/oc_engine.h"
+#include "oc_observe.h"
 #include "oc_rollout.h"
 #include "oc_swar.h"
 
@@ -1854,6 +1856,13 @@ struct oc_handle {
     uint8_t* wide_tiles = nullptr;   // device: tile class per cell (W * H rounded up to 4 bytes)
     uint8_t wide_tiles_host[ocro::kMaxCellsWide];
     int32_t lik_form = OC_LIK_FORM_AUTO;  // oc_set_likelihood_form
+    // oc_observe: the tile class per cell (W * H rounded up to 4 bytes), then the static list: the
+    // element offset (class - 1) * W * H + cell of every non-Floor square, u16 each
+    std::vector<uint8_t> obs_tab_host;
+    uint8_t* obs_tab = nullptr;      // device copy
+    int32_t obs_static_off = 0, obs_nstatic = 0;
+    int32_t obs_nt = 0;              // non-temporal output stores (OC_OBS_STORES=nt|plain overrides)
+    int32_t obs_tile = ocob::kMaxTileEnvs;  // envs per block at most (OC_OBS_TILE=64|32|16|... overrides)
     mutable std::string last_error;       // oc_get_last_error: the last failed call on this handle
 };
 
@@ -2211,6 +2220,30 @@ int oc_create(const oc_level_desc* lv, int32_t num_agents, int32_t max_T, int32_
             (void)hipGetLastError();
         }
     }
+    {  // oc_observe's level table
+        const int cells = W * H, off = (cells + 3) & ~3;
+        std::vector<uint16_t> st;
+        for (int c = 0; c < cells; ++c)
+            if (lv->tiles[c] != OC_TILE_FLOOR) st.push_back((uint16_t)((lv->tiles[c] - 1) * cells + c));
+        h->obs_static_off = off;
+        h->obs_nstatic = (int32_t)st.size();
+        h->obs_tab_host.assign((size_t)off + 2 * st.size() + 2, 0);
+        memcpy(h->obs_tab_host.data(), lv->tiles, (size_t)cells);
+        if (!st.empty()) memcpy(h->obs_tab_host.data() + off, st.data(), 2 * st.size());
+        if (const char* e = getenv("OC_OBS_STORES")) h->obs_nt = strcmp(e, "nt") == 0 ? 1 : 0;
+        if (const char* e = getenv("OC_OBS_TILE")) {  // measurement knob: a power of two up to kMaxTileEnvs
+            const int v = atoi(e);
+            if (v >= 1 && v <= ocob::kMaxTileEnvs && (v & (v - 1)) == 0) h->obs_tile = v;
+        }
+        if (!host_only) {
+            if (hipSetDevice(device) != hipSuccess || hipMalloc(&h->obs_tab, h->obs_tab_host.size()) != hipSuccess ||
+                hipMemcpy(h->obs_tab, h->obs_tab_host.data(), h->obs_tab_host.size(), hipMemcpyHostToDevice) !=
+                    hipSuccess) {
+                h->obs_tab = nullptr;  // no device: oc_cpu_observe only
+                (void)hipGetLastError();
+            }
+        }
+    }
     *out = h;
     return OC_OK;
 }
@@ -2259,6 +2292,7 @@ int oc_reachability16(const oc_handle* h, int32_t* num_nodes, uint16_t* node_of,
 int oc_destroy(oc_handle* h) {
     if (h != nullptr && h->roll_blob != nullptr) (void)hipFree(h->roll_blob);
     if (h != nullptr && h->wide_tiles != nullptr) (void)hipFree(h->wide_tiles);
+    if (h != nullptr && h->obs_tab != nullptr) (void)hipFree(h->obs_tab);
     delete h;
     return OC_OK;
 }
@@ -2867,6 +2901,110 @@ int oc_render_ordered(const oc_handle* h, const void* state, const uint8_t* draw
                        atlas, background, out)
     OC_DISPATCH_W(h, OC_LAUNCH_RENDER)
     return hip_check("oc_render launch");
+}
+
+// oc_observe / oc_cpu_observe: the arguments both check, and the level's side of ObsArgs
+static int observe_args(const oc_handle* h, const void* state, const void* obs, const uint8_t* action_mask,
+                        int32_t dtype, int32_t view_agent, int64_t B, ocob::ObsArgs& R) {
+    if (state == nullptr || B < 0) return fail(OC_EINVAL, "bad argument");
+    if (obs == nullptr && action_mask == nullptr) return fail(OC_EINVAL, "observe: obs and action_mask are both NULL");
+    if (dtype != OC_OBS_U8 && dtype != OC_OBS_F16) return fail(OC_EINVAL, "observe: dtype %d (OC_OBS_U8 or OC_OBS_F16)", dtype);
+    if (view_agent < -1 || view_agent >= h->A)
+        return fail(OC_EINVAL, "observe: view_agent %d outside [-1, %d)", view_agent, h->A);
+    if (((uintptr_t)state & 15u) || ((uintptr_t)action_mask & 3u) || (dtype == OC_OBS_F16 && ((uintptr_t)obs & 1u)))
+        return fail(OC_EINVAL, "misaligned buffer");
+    R = ocob::ObsArgs{};
+    R.W = h->level.width;
+    R.H = h->level.height;
+    R.HW = R.W * R.H;
+    R.C = OC_OBS_CHANNELS(h->A);
+    R.CHW = R.C * R.HW;
+    R.counts = h->level.encoding == OC_ENC_COUNTS;
+    R.rot = view_agent < 0 ? 0 : view_agent;
+    R.nstatic = h->obs_nstatic;
+    R.nt = h->obs_nt;
+    R.pitch = pitch_for(B);
+    R.B = B;
+    return OC_OK;
+}
+
+int oc_observe(const oc_handle* h, const void* state, void* obs, uint8_t* action_mask, int32_t dtype,
+               int32_t view_agent, int64_t B, void* stream) {
+    if (h == nullptr) return fail(OC_EINVAL, "bad argument");
+    ErrScope es_(h);
+    OC_NEED_DEVICE(h);
+    ocob::ObsArgs R;
+    if (const int rc = observe_args(h, state, obs, action_mask, dtype, view_agent, B, R)) return rc;
+    if (h->obs_tab == nullptr) return fail(OC_EHIP, "observe: the level table is not on the device");
+    if (B == 0) return OC_OK;
+    // envs per tile: the largest power of two whose tile and staging fit the LDS budget (a 7x7
+    // kitchen: 64; the largest wide levels: 1, every tile then with a head and a tail)
+    const int planes = 3 * h->A + (h->wide ? 3 : 2) * h->K;
+    int E = h->obs_tile, lg = 31 - __builtin_clz((unsigned)h->obs_tile), lds = 0;
+    for (;; E >>= 1, --lg) {
+        R.lds_state = (E * R.CHW + 16 + 15) & ~15;
+        R.lds_tiles = R.lds_state + ((planes * E + 3) & ~3);
+        R.lds_statics = R.lds_tiles + ((R.HW + 3) & ~3);
+        R.lds_mask = R.lds_statics + ((2 * R.nstatic + 3) & ~3);
+        lds = R.lds_mask + ((h->A * E + 3) & ~3);
+        if (lds <= ocob::kLdsBudget || E == 1) break;
+    }
+    if (lds > ocob::kLdsBudget) return fail(OC_ELEVEL, "observe: one env's planes (%d B) exceed the LDS budget", lds);
+    R.tile_envs = E;
+    R.log2_envs = lg;
+    // a persistent grid: the blocks the CUs' LDS holds at once (at most 8 of 4 waves per CU)
+    const int64_t tiles = (B + E - 1) / E;
+    int per_cu = kLdsPerCu / (lds + 512);
+    per_cu = per_cu > 8 ? 8 : per_cu;
+    const int64_t resident = (int64_t)h->cus * per_cu;
+    const dim3 grid((unsigned)(tiles < resident ? tiles : resident));
+    hipStream_t st = (hipStream_t)stream;
+    const uint8_t* tab = h->obs_tab;
+    const uint16_t* statics = (const uint16_t*)(h->obs_tab + h->obs_static_off);
+#define OC_LAUNCH_OBS(A, K, WD)                                                                                   \
+    if (dtype == OC_OBS_F16)                                                                                      \
+        hipLaunchKernelGGL((ocob::oc_observe_kernel<A, K, WD, true>), grid, dim3(ocob::kBlock), lds, st, R,       \
+                           (const uint8_t*)state, tab, statics, (uint8_t*)obs, action_mask);                      \
+    else                                                                                                          \
+        hipLaunchKernelGGL((ocob::oc_observe_kernel<A, K, WD, false>), grid, dim3(ocob::kBlock), lds, st, R,      \
+                           (const uint8_t*)state, tab, statics, (uint8_t*)obs, action_mask)
+    OC_DISPATCH_W(h, OC_LAUNCH_OBS)
+#undef OC_LAUNCH_OBS
+    return hip_check("oc_observe launch");
+}
+
+int oc_cpu_observe(const oc_handle* h, const void* state, void* obs, uint8_t* action_mask, int32_t dtype,
+                   int32_t view_agent, int64_t B, int32_t nthreads) {
+    if (h == nullptr || nthreads < 0) return fail(OC_EINVAL, "bad argument");
+    ErrScope es_(h);
+    ocob::ObsArgs R;
+    if (const int rc = observe_args(h, state, obs, action_mask, dtype, view_agent, B, R)) return rc;
+    if (B == 0) return OC_OK;
+    if (nthreads == 0) nthreads = (int32_t)std::thread::hardware_concurrency();
+    int64_t nt = nthreads < 1 ? 1 : nthreads;
+    if (nt > (B + 16383) / 16384) nt = (B + 16383) / 16384;  // >= 16 Ki envs per thread
+    if (nt < 1) nt = 1;
+    const uint8_t* tab = h->obs_tab_host.data();
+    const uint16_t* statics = (const uint16_t*)(tab + h->obs_static_off);
+    auto run = [&](int64_t i) {
+        const int64_t e0 = B * i / nt, e1 = B * (i + 1) / nt;
+#define OC_CPU_OBS(A, K, WD) \
+    ocob::cpu_observe_range<A, K, WD>(R, tab, statics, (const uint8_t*)state, obs, action_mask, dtype == OC_OBS_F16, e0, e1)
+        OC_DISPATCH_W(h, OC_CPU_OBS)
+#undef OC_CPU_OBS
+        return OC_OK;
+    };
+    // ranges 1..nt-1 on workers, range 0 (and any whose thread cannot start) on the calling thread
+    std::vector<std::thread> pool;
+    int64_t started = 1;
+    try {
+        for (; started < nt; ++started) pool.emplace_back([&, i = started] { (void)run(i); });
+    } catch (const std::exception&) {
+    }
+    const int rc = run(0);
+    for (int64_t i = started; i < nt; ++i) (void)run(i);
+    for (auto& t : pool) t.join();
+    return rc;
 }
 
 int oc_gen_actions(const oc_handle* h, uint8_t* actions, int64_t B, int64_t env_offset, int64_t step,

@@ -21,7 +21,7 @@ OC_MAX_NARROW_CELLS = 255   # up to this many cells: byte cell ids; more ("wide"
 OC_MAX_GOALS = 4
 OC_PITCH_ALIGN = 4096
 OC_NSTATS = 5
-OC_ABI_VERSION = 10  # include/oc_engine.h
+OC_ABI_VERSION = 11  # include/oc_engine.h
 OC_DEVICE_HOST = -1  # oc_create: a host-only handle (no HIP call)
 OC_LIK_FORM_AUTO, OC_LIK_FORM_GROUPED = 0, 1
 OC_EINVAL, OC_EHIP, OC_ELEVEL = -1, -2, -3
@@ -37,8 +37,18 @@ EXPORTED_SYMBOLS = (
     "oc_abi_version", "oc_last_error", "oc_create", "oc_destroy", "oc_get_layout", "oc_reset",
     "oc_step", "oc_step_n", "oc_cpu_step", "oc_rollout", "oc_nav_likelihood", "oc_subtask_bounds", "oc_reachability", "oc_reachability16", "oc_render", "oc_render_ordered",
     "oc_gen_actions", "oc_state_checksum", "oc_stats_size", "oc_stats_reduce", "oc_get_last_error",
-    "oc_set_likelihood_form",
+    "oc_set_likelihood_form", "oc_observe", "oc_cpu_observe",
 )
+
+
+# oc_observe: grid feature planes (3 static + 7 item + A agent channels) and legal-move masks
+OC_OBS_STATIC, OC_OBS_ITEM = 3, 7
+OC_OBS_U8, OC_OBS_F16 = 0, 1
+
+
+def obs_channels(A: int) -> int:
+    """C of oc_observe's [B][C][H][W] planes (OC_OBS_CHANNELS)."""
+    return OC_OBS_STATIC + OC_OBS_ITEM + A
 
 
 class OcLevelDesc(ctypes.Structure):
@@ -206,6 +216,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.oc_get_last_error.argtypes = [vp, ctypes.c_char_p, i64]
     lib.oc_set_likelihood_form.restype = ctypes.c_int
     lib.oc_set_likelihood_form.argtypes = [vp, i32]
+    lib.oc_observe.restype = ctypes.c_int
+    lib.oc_observe.argtypes = [vp, vp, vp, vp, i32, i32, i64, vp]
+    lib.oc_cpu_observe.restype = ctypes.c_int
+    lib.oc_cpu_observe.argtypes = [vp, vp, vp, vp, i32, i32, i64, i32]
     lib.oc_cpu_step.restype = ctypes.c_int
     lib.oc_cpu_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i32]
     lib.oc_step_n.restype = ctypes.c_int

@@ -19,6 +19,7 @@ from . import levels as _levels
 
 
 _U64 = (torch.uint64, torch.int64)
+_OBS_DTYPES = {torch.uint8: capi.OC_OBS_U8, torch.float16: capi.OC_OBS_F16}
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -96,6 +97,17 @@ class OvercookedBatch:
         leaves them zero): zero it again after a faulted launch, and do not share one buffer
         between concurrent step_n calls on different streams."""
         return torch.zeros(self.stats_bytes // 8, dtype=torch.uint64, device=self.device)
+
+    def new_obs(self, dtype=torch.uint8) -> torch.Tensor:
+        """[B, C, H, W] observation planes (oc_observe): torch.uint8 or torch.float16."""
+        if dtype not in _OBS_DTYPES:
+            raise TypeError("observation dtype %s, expected torch.uint8 or torch.float16" % dtype)
+        return torch.empty((self.B, capi.obs_channels(self.A), self.level.height, self.level.width), dtype=dtype,
+                           device=self.device)
+
+    def new_action_mask(self) -> torch.Tensor:
+        """[A * pitch] u8 legal-move masks (oc_observe): agent a's envs at [a * pitch, a * pitch + B)."""
+        return torch.empty(self.A * self.pitch, dtype=torch.uint8, device=self.device)
 
     def planes(self, state: torch.Tensor) -> Dict[str, torch.Tensor]:
         """Named views of a state buffer ([A|K, pitch] u8 planes; t is [pitch] u16)."""
@@ -247,6 +259,37 @@ class OvercookedBatch:
                 self._stream())
         return _bound(self.lib.oc_subtask_bounds, args)
 
+    def observe(self, state: torch.Tensor, obs: Optional[torch.Tensor] = None,
+                action_mask: Optional[torch.Tensor] = None, view_agent: int = -1):
+        """Grid observation and legal-move masks of every env (oc_observe): `obs` [B, C, H, W]
+        (C = 10 + A: Counter, Cutboard, Delivery, Fresh/Chopped Tomato, Lettuce, Onion, Plate, the
+        agents; u8 or float16, taken from the tensor) and `action_mask` u8 [A * pitch] (bit k:
+        World.NAV_ACTIONS[k] is in get_single_actions, navigation_planner/utils.py:55-90; bit 4
+        always).  With `view_agent` a the agent channels are rotated so that agent a is channel
+        10.  Given one output only that one is computed; given neither, both are allocated (u8).
+        Returns (obs, action_mask)."""
+        if obs is None and action_mask is None:
+            obs, action_mask = self.new_obs(), self.new_action_mask()
+        self.observe_launcher(state, obs, action_mask, view_agent)()
+        return obs, action_mask
+
+    def observe_launcher(self, state: torch.Tensor, obs: Optional[torch.Tensor],
+                         action_mask: Optional[torch.Tensor], view_agent: int = -1):
+        """An oc_observe call bound once (see rollout_launcher)."""
+        self._check(state, self.layout.state_bytes)
+        dtype = capi.OC_OBS_U8
+        if obs is not None:
+            if obs.dtype not in _OBS_DTYPES:
+                raise TypeError("observation dtype %s, expected torch.uint8 or torch.float16" % obs.dtype)
+            n = self.B * capi.obs_channels(self.A) * self.level.height * self.level.width
+            if obs.device != self.device or not obs.is_contiguous() or obs.numel() < n:
+                raise ValueError("obs must be contiguous on %s with at least %d elements" % (self.device, n))
+            dtype = _OBS_DTYPES[obs.dtype]
+        if action_mask is not None:
+            self._check(action_mask, self.A * self.pitch)
+        args = (self._h, _ptr(state), _ptr(obs), _ptr(action_mask), dtype, int(view_agent), self.B, self._stream())
+        return _bound(self.lib.oc_observe, args)
+
     def set_likelihood_form(self, form: int) -> None:
         """oc_set_likelihood_form: capi.OC_LIK_FORM_AUTO (default) or OC_LIK_FORM_GROUPED (the
         grouped likelihood kernel on any level; the same outputs, for its parity test)."""
@@ -359,3 +402,20 @@ class CpuStepper:
         capi.check(self.lib.oc_cpu_step(self._h, p(state_in), p(state_out), p(actions), p(exec_out), p(coll),
                                         p(totals), self.B, self.nthreads))
         return state_out
+
+    def observe(self, state: np.ndarray, dtype=np.uint8, view_agent: int = -1, want_mask: bool = True):
+        """oc_cpu_observe: the grid observation [B, C, H, W] (np.uint8 or np.float16) and, with
+        `want_mask`, the legal-move masks u8 [A, pitch] (columns past B zero) of the host states;
+        mirrors OvercookedBatch.observe.  Returns (obs, action_mask or None)."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.uint8), np.dtype(np.float16)):
+            raise TypeError("observation dtype %s, expected uint8 or float16" % dt)
+        if state.dtype != np.uint8 or not state.flags.c_contiguous or state.nbytes < self.layout.state_bytes:
+            raise ValueError("host buffers: contiguous uint8 of at least %d bytes" % self.layout.state_bytes)
+        obs = np.empty((self.B, capi.obs_channels(self.A), self.level.height, self.level.width), dt)
+        mask = np.zeros((self.A, self.pitch), np.uint8) if want_mask else None
+        capi.check(self.lib.oc_cpu_observe(self._h, state.ctypes.data, obs.ctypes.data,
+                                           None if mask is None else mask.ctypes.data,
+                                           capi.OC_OBS_F16 if dt == np.float16 else capi.OC_OBS_U8, int(view_agent),
+                                           self.B, self.nthreads))
+        return obs, mask

@@ -785,6 +785,14 @@ class OvercookedVecEnv:
     where ``info`` holds the executed actions ``[A, B]`` and the collision-pair masks ``[B]``.
     Envs that were done at the input are reset to the level template by the engine in the
     same launch (next-step auto-reset).  All tensors stay on the GPU.
+
+    ``observe(dtype, view_agent)`` returns the grid observation ``[B, C, H, W]`` of the current
+    states (``C = 10 + A`` count planes: Counter, Cutboard, Delivery, Fresh/Chopped Tomato,
+    Lettuce, Onion, Plate, one per agent; ``uint8`` or ``float16``; with ``view_agent = a`` the
+    agent planes are rotated so that agent a is plane 10), and ``action_mask()`` the legal moves
+    ``uint8 [A, B]`` (bit k: ``World.NAV_ACTIONS[k]`` is in the reference's
+    ``get_single_actions``; bit 4, the no-op, always).  Both reuse their buffers between calls
+    (oc_observe); ``render()`` gives the reference's 560x560 image instead, at 1,600 times the bytes.
     """
 
     def __init__(self, level, num_agents: int, num_envs: int, max_num_timesteps: int = 100, device="cuda:0"):
@@ -833,6 +841,24 @@ class OvercookedVecEnv:
             from .render import Renderer
             self._renderer = Renderer(self.batch)
         return self._renderer.render(self.state, channels=channels, draw_rank=draw_rank)
+
+    def observe(self, dtype=torch.uint8, view_agent: int = -1) -> torch.Tensor:
+        """[B, C, H, W] grid observation of the current states (oc_observe; the class docstring
+        lists the planes).  The tensor is this env's buffer for `dtype`, rewritten by the next call."""
+        bufs = self.__dict__.setdefault("_obs", {})
+        if dtype not in bufs:
+            bufs[dtype] = self.batch.new_obs(dtype)
+        self.batch.observe(self.state, obs=bufs[dtype], view_agent=view_agent)
+        return bufs[dtype]
+
+    def action_mask(self) -> torch.Tensor:
+        """u8 [A, B] legal-move masks of the current states (oc_observe): bit k set iff
+        World.NAV_ACTIONS[k] is in get_single_actions(env, agent), bit 4 (no-op) always.  A view of
+        this env's buffer, rewritten by the next call."""
+        if getattr(self, "_mask", None) is None:
+            self._mask = self.batch.new_action_mask()
+        self.batch.observe(self.state, action_mask=self._mask)
+        return self._mask.view(self.A, self.P)[:, :self.num_envs]
 
     def episode_stats(self) -> torch.Tensor:
         """int64 [episodes, successes, steps, collisions, errors] since construction."""

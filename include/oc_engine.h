@@ -11,6 +11,8 @@
  *   oc_step, oc_step_n       <- OvercookedEnvironment.step       (overcooked_environment.py:255-306)
  *                               = check_collisions (:724-762) + execute_navigation/interact
  *                               (:767-770, gym_cooking/utils/interact.py:4-89) + done/reward (:316-376)
+ *   oc_observe, oc_cpu_observe <- a grid encoding of world.objects / sim_agents (utils/core.py:28-305) and
+ *                               get_single_actions (gym_cooking/navigation_planner/utils.py:55-90) per agent
  *   oc_gen_actions           <- synthetic action streams (the reference env has no RNG)
  *   oc_stats_*               <- the per-episode bookkeeping main.py keeps in its metrics Bag
  *                               (gym_cooking/misc/metrics/metrics_bag.py:40-72), reduced per GPU
@@ -41,7 +43,7 @@
 extern "C" {
 #endif
 
-#define OC_ABI_VERSION 10
+#define OC_ABI_VERSION 11
 
 #define OC_MAX_AGENTS 4
 #define OC_MAX_ITEMS 16  /* item slots: K = 4, 8 or 16 per level */
@@ -436,6 +438,61 @@ int oc_render(const oc_handle* h, const void* state, const uint32_t* atlas, cons
 int oc_render_ordered(const oc_handle* h, const void* state, const uint8_t* draw_rank, const uint32_t* atlas,
                       const uint32_t* background, const oc_render_desc* desc, uint8_t* out, int64_t B,
                       void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Grid observation and legal-move masks (ABI 11): what a batched policy reads per env, at a
+ * size a step can afford (a 7x7 kitchen with two agents: 588 B in u8; the image is 940,800 B).
+ *
+ * obs[e][c][y][x], C = OC_OBS_CHANNELS(A) planes of H x W small counts, a pure function of env
+ * e's state and the level:
+ *   0, 1, 2   Counter, Cutboard, Delivery: 1 on squares of that class (the GridSquare subclasses
+ *             in world.objects, gym_cooking/utils/core.py:28-120); Floor is all-zero
+ *   3, 4      FreshTomato, ChoppedTomato: for every Object in world.objects, held or not, at
+ *   5, 6      FreshLettuce, ChoppedLettuce   obj.location (a held object carries its holder's
+ *   7, 8      FreshOnion, ChoppedOnion       location): +1 per content of that food in that
+ *   9         Plate                          state / per Plate content (core.py:130-305)
+ *   10 + i    agent i: 1 at sim_agents[i].location
+ * Dead item slots contribute nothing; several objects on one square add up (delivered dishes;
+ * two tomatoes in one dish of an OC_ENC_COUNTS level give 2); both content encodings decode to
+ * the same channels (OC_ENC_COUNTS: OC_MC_FRESH marks a single fresh food, every other food is
+ * chopped).  t and the flags are not encoded (the caller has their planes); DONE and ERR envs
+ * are encoded as their stored state is.
+ *   view_agent : -1: agent channels in index order; a in [0, A): agent i is channel
+ *                10 + ((i - a) mod A), so the viewing agent is always channel 10
+ *
+ * action_mask[a][e], u8: bit k (k = 0..3) is set iff World.NAV_ACTIONS[k] is in
+ * get_single_actions(env, sim_agents[a]) (gym_cooking/navigation_planner/utils.py:55-90) on the
+ * full env: every agent present, no agent's square may be entered (the agent's own included,
+ * which matters where World.inbounds, utils/world.py:432-436, clamps an off-grid target onto
+ * it), Floor and Delivery are open, a Counter or Cutboard is legal as a put-down, a pick-up
+ * or a merge (core.mergeable, core.py:222-241).  Bit OC_ACT_NOOP is always set.
+ * ------------------------------------------------------------------------------------- */
+#define OC_OBS_STATIC 3
+#define OC_OBS_ITEM 7
+#define OC_OBS_CHANNELS(A) (OC_OBS_STATIC + OC_OBS_ITEM + (A))
+#define OC_OBS_U8 0
+#define OC_OBS_F16 1
+
+/*   state       : B states (oc_layout), device memory
+ *   obs         : nullable; device [B][C][H][W], contiguous, env-major (torch NCHW), u8
+ *                 (OC_OBS_U8) or IEEE half (OC_OBS_F16; the counts are exact).  Exactly B*C*H*W
+ *                 elements are written, not one byte past them; any element-aligned address
+ *                 (16-byte alignment keeps every store full width); more than 4 GiB is fine
+ *   action_mask : nullable; device u8 [A][pitch].  Columns past B as exec_actions: the batch's
+ *                 last 4-env word may be completed (no-op only), nothing at or past the next
+ *                 multiple of 4 above B is written
+ *   dtype       : OC_OBS_U8 or OC_OBS_F16;  view_agent : -1 or 0..A-1
+ * Both outputs NULL, another dtype or view_agent is OC_EINVAL.  Stream-ordered, no allocation,
+ * no synchronisation (hipGraph-capturable, as oc_step); one launch for both outputs. */
+int oc_observe(const oc_handle* h, const void* state, void* obs, uint8_t* action_mask,
+               int32_t dtype, int32_t view_agent, int64_t B, void* stream);
+
+/* The same on the host (what oc_cpu_step is to oc_step): HOST buffers, works on OC_DEVICE_HOST
+ * handles, the kernel's decode compiled for the host, threaded over env ranges (nthreads 0 = the
+ * host's hardware threads; at least 16 Ki envs each).  Columns of action_mask past B are not
+ * written.  It never touches the device; oc_observe never calls it. */
+int oc_cpu_observe(const oc_handle* h, const void* state, void* obs, uint8_t* action_mask,
+                   int32_t dtype, int32_t view_agent, int64_t B, int32_t nthreads);
 
 #ifdef __cplusplus
 }
