@@ -18,6 +18,7 @@
 //   oc_bounds_kernel  full-state subtask lower bounds + allocation feasibility (oc_subtask_bounds).
 //   oc_render_kernel  image observations.
 //   oc_observe_kernel grid feature planes + legal-move masks per env (oc_observe.h).
+//   oc_progress_kernel per-subtask object counts, completion events, shaped reward (oc_progress.h).
 //   reset / gen_actions / checksum / stats_reduce helpers.
 // All of them accumulate nothing on the host; statistics are per-block rows of no-return
 // 64-bit atomics reduced by oc_stats_reduce for the all-gather of episode summaries.
@@ -34,6 +35,7 @@
 
 #include "../../include/oc_engine.h"
 #include "oc_observe.h"
+#include "oc_progress.h"
 #include "oc_rollout.h"
 #include "oc_swar.h"
 
@@ -2992,6 +2994,99 @@ int oc_cpu_observe(const oc_handle* h, const void* state, void* obs, uint8_t* ac
     ocob::cpu_observe_range<A, K, WD>(R, tab, statics, (const uint8_t*)state, obs, action_mask, dtype == OC_OBS_F16, e0, e1)
         OC_DISPATCH_W(h, OC_CPU_OBS)
 #undef OC_CPU_OBS
+        return OC_OK;
+    };
+    // ranges 1..nt-1 on workers, range 0 (and any whose thread cannot start) on the calling thread
+    std::vector<std::thread> pool;
+    int64_t started = 1;
+    try {
+        for (; started < nt; ++started) pool.emplace_back([&, i = started] { (void)run(i); });
+    } catch (const std::exception&) {
+    }
+    const int rc = run(0);
+    for (int64_t i = started; i < nt; ++i) (void)run(i);
+    for (auto& t : pool) t.join();
+    return rc;
+}
+
+// oc_progress / oc_cpu_progress: the arguments both check, and the call's ProgArgs
+static int progress_args(const oc_handle* h, const void* state_prev, const void* states, int32_t n,
+                         const oc_subtask* subtasks, int32_t num_subtasks, const float* weights, const uint8_t* counts,
+                         const uint8_t* events, const float* reward, int64_t B, ocpg::ProgArgs& R) {
+    if (state_prev == nullptr || states == nullptr || subtasks == nullptr || B < 0) return fail(OC_EINVAL, "bad argument");
+    if (n < 1) return fail(OC_EINVAL, "progress: n = %d (at least 1)", n);
+    if (num_subtasks < 1 || num_subtasks > OC_MAX_SUBTASKS)
+        return fail(OC_EINVAL, "progress: num_subtasks %d outside [1, %d]", num_subtasks, OC_MAX_SUBTASKS);
+    if (counts == nullptr && events == nullptr && reward == nullptr)
+        return fail(OC_EINVAL, "progress: counts, events and reward are all NULL");
+    if (((uintptr_t)state_prev & 3u) || ((uintptr_t)states & 3u) || ((uintptr_t)counts & 3u) ||
+        ((uintptr_t)events & 3u) || ((uintptr_t)reward & 15u))
+        return fail(OC_EINVAL, "misaligned buffer");
+    R = ocpg::ProgArgs{};
+    for (int i = 0; i < num_subtasks; ++i) {
+        const int32_t kind = subtasks[i].kind;
+        if (kind != OC_SUB_NONE && kind != OC_SUB_CHOP && kind != OC_SUB_MERGE && kind != OC_SUB_DELIVER)
+            return fail(OC_EINVAL, "progress: subtask %d has kind %d", i, kind);
+        R.sub[i] = (uint32_t)kind << 8 | subtasks[i].goal_mask;
+        R.weight[i] = weights != nullptr ? weights[i] : 1.0f;
+    }
+    R.W = h->level.width;
+    R.tile_words = (h->level.width * h->level.height + 3) / 4;
+    R.n = n;
+    R.S = num_subtasks;
+    R.planes = OC_PROGRESS_EVENT_PLANES(num_subtasks);
+    R.pitch = pitch_for(B);
+    R.B = B;
+    R.state_bytes = (int64_t)(3 * h->A + (h->wide ? 3 : 2) * h->K + 3) * R.pitch;
+    return OC_OK;
+}
+
+int oc_progress(const oc_handle* h, const void* state_prev, const void* states, int32_t n, const oc_subtask* subtasks,
+                int32_t num_subtasks, const float* weights, uint8_t* counts, uint8_t* events, float* reward, int64_t B,
+                void* stream) {
+    if (h == nullptr) return fail(OC_EINVAL, "bad argument");
+    ErrScope es_(h);
+    OC_NEED_DEVICE(h);
+    ocpg::ProgArgs R;
+    if (const int rc = progress_args(h, state_prev, states, n, subtasks, num_subtasks, weights, counts, events, reward, B, R))
+        return rc;
+    if (h->obs_tab == nullptr) return fail(OC_EHIP, "progress: the level table is not on the device");
+    if (B == 0) return OC_OK;
+    // one lane per word of the batch (four envs), whatever n: a lane walks its envs' n states
+    const int64_t lanes = (B + 3) / 4;
+    const dim3 grid((unsigned)((lanes + ocpg::kBlock - 1) / ocpg::kBlock));
+    hipStream_t st = (hipStream_t)stream;
+#define OC_LAUNCH_PROG(A, K, WD)                                                                              \
+    hipLaunchKernelGGL((ocpg::oc_progress_kernel<A, K, WD>), grid, dim3(ocpg::kBlock), 0, st, R, h->obs_tab, \
+                       (const uint8_t*)state_prev, (const uint8_t*)states, counts, events, reward)
+    OC_DISPATCH_W(h, OC_LAUNCH_PROG)
+#undef OC_LAUNCH_PROG
+    return hip_check("oc_progress launch");
+}
+
+int oc_cpu_progress(const oc_handle* h, const void* state_prev, const void* states, int32_t n,
+                    const oc_subtask* subtasks, int32_t num_subtasks, const float* weights, uint8_t* counts,
+                    uint8_t* events, float* reward, int64_t B, int32_t nthreads) {
+    if (h == nullptr || nthreads < 0) return fail(OC_EINVAL, "bad argument");
+    ErrScope es_(h);
+    ocpg::ProgArgs R;
+    if (const int rc = progress_args(h, state_prev, states, n, subtasks, num_subtasks, weights, counts, events, reward, B, R))
+        return rc;
+    if (B == 0) return OC_OK;
+    if (nthreads == 0) nthreads = (int32_t)std::thread::hardware_concurrency();
+    int64_t nt = nthreads < 1 ? 1 : nthreads;
+    if (nt > (B + 16383) / 16384) nt = (B + 16383) / 16384;  // >= 16 Ki envs per thread
+    if (nt < 1) nt = 1;
+    uint8_t tab[ocpg::kTableBytes];
+    ocpg::build_table(h->obs_tab_host.data(), R.tile_words, tab);
+    const int64_t words = (B + 3) / 4;
+    auto run = [&](int64_t i) {
+        const int64_t g0 = words * i / nt, g1 = words * (i + 1) / nt;
+#define OC_CPU_PROG(A, K, WD)                                                                                      \
+    ocpg::cpu_progress_words<A, K, WD>(R, tab, (const uint8_t*)state_prev, (const uint8_t*)states, counts, events, \
+                                       reward, g0, g1)
+        OC_DISPATCH_W(h, OC_CPU_PROG)
+#undef OC_CPU_PROG
         return OC_OK;
     };
     // ranges 1..nt-1 on workers, range 0 (and any whose thread cannot start) on the calling thread

@@ -21,7 +21,7 @@ OC_MAX_NARROW_CELLS = 255   # up to this many cells: byte cell ids; more ("wide"
 OC_MAX_GOALS = 4
 OC_PITCH_ALIGN = 4096
 OC_NSTATS = 5
-OC_ABI_VERSION = 11  # include/oc_engine.h
+OC_ABI_VERSION = 12  # include/oc_engine.h
 OC_DEVICE_HOST = -1  # oc_create: a host-only handle (no HIP call)
 OC_LIK_FORM_AUTO, OC_LIK_FORM_GROUPED = 0, 1
 OC_EINVAL, OC_EHIP, OC_ELEVEL = -1, -2, -3
@@ -37,7 +37,7 @@ EXPORTED_SYMBOLS = (
     "oc_abi_version", "oc_last_error", "oc_create", "oc_destroy", "oc_get_layout", "oc_reset",
     "oc_step", "oc_step_n", "oc_cpu_step", "oc_rollout", "oc_nav_likelihood", "oc_subtask_bounds", "oc_reachability", "oc_reachability16", "oc_render", "oc_render_ordered",
     "oc_gen_actions", "oc_state_checksum", "oc_stats_size", "oc_stats_reduce", "oc_get_last_error",
-    "oc_set_likelihood_form", "oc_observe", "oc_cpu_observe",
+    "oc_set_likelihood_form", "oc_observe", "oc_cpu_observe", "oc_progress", "oc_cpu_progress",
 )
 
 
@@ -49,6 +49,12 @@ OC_OBS_U8, OC_OBS_F16 = 0, 1
 def obs_channels(A: int) -> int:
     """C of oc_observe's [B][C][H][W] planes (OC_OBS_CHANNELS)."""
     return OC_OBS_STATIC + OC_OBS_ITEM + A
+
+
+def event_planes(n: int) -> int:
+    """Byte planes of oc_progress's events for n subtasks (OC_PROGRESS_EVENT_PLANES): bit b of
+    plane c is subtask 8c + b."""
+    return (n + 7) // 8
 
 
 class OcLevelDesc(ctypes.Structure):
@@ -114,6 +120,27 @@ def subtask(kind: int, agents, start_masks, goal_mask: int, goal_count: int = 0,
     s.goal_mask = goal_mask
     s.goal_count = goal_count
     return s
+
+
+def progress_subtasks(subtasks, enc: int):
+    """oc_subtask rows for oc_progress from recipe subtasks (recipes.Subtask, or None): only the
+    kind and the goal mask are read there (recipes.subtask_masks in the mask encoding `enc`)."""
+    from . import recipes as _rc
+    rows = []
+    for st in subtasks:
+        kind, starts, goal = _rc.subtask_masks(st, enc)
+        rows.append(subtask(kind, [0], list(starts), goal))
+    return rows
+
+
+def weight_array(weights, n: int):
+    """A host float[n] for oc_progress, or None (all 1.0)."""
+    if weights is None:
+        return None
+    w = [float(x) for x in weights]
+    if len(w) != n:
+        raise ValueError("weights: %d values for %d subtasks" % (len(w), n))
+    return (ctypes.c_float * n)(*w)
 
 
 def subtask_array(subtasks):
@@ -220,6 +247,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.oc_observe.argtypes = [vp, vp, vp, vp, i32, i32, i64, vp]
     lib.oc_cpu_observe.restype = ctypes.c_int
     lib.oc_cpu_observe.argtypes = [vp, vp, vp, vp, i32, i32, i64, i32]
+    lib.oc_progress.restype = ctypes.c_int
+    lib.oc_progress.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, i64, vp]
+    lib.oc_cpu_progress.restype = ctypes.c_int
+    lib.oc_cpu_progress.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, i64, i32]
     lib.oc_cpu_step.restype = ctypes.c_int
     lib.oc_cpu_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i32]
     lib.oc_step_n.restype = ctypes.c_int

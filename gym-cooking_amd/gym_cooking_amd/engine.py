@@ -109,6 +109,14 @@ class OvercookedBatch:
         """[A * pitch] u8 legal-move masks (oc_observe): agent a's envs at [a * pitch, a * pitch + B)."""
         return torch.empty(self.A * self.pitch, dtype=torch.uint8, device=self.device)
 
+    def new_progress_buffers(self, num_subtasks: int, n: int = 1):
+        """(counts u8 [n, S, pitch], events u8 [n, planes, pitch], reward f32 [n, pitch]) for
+        oc_progress over `num_subtasks` subtasks and n steps."""
+        P = self.pitch
+        return (torch.empty((n, num_subtasks, P), dtype=torch.uint8, device=self.device),
+                torch.empty((n, capi.event_planes(num_subtasks), P), dtype=torch.uint8, device=self.device),
+                torch.empty((n, P), dtype=torch.float32, device=self.device))
+
     def planes(self, state: torch.Tensor) -> Dict[str, torch.Tensor]:
         """Named views of a state buffer ([A|K, pitch] u8 planes; t is [pitch] u16)."""
         L, P, A, K = self.layout, self.pitch, self.A, self.K
@@ -290,6 +298,39 @@ class OvercookedBatch:
         args = (self._h, _ptr(state), _ptr(obs), _ptr(action_mask), dtype, int(view_agent), self.B, self._stream())
         return _bound(self.lib.oc_observe, args)
 
+    def progress(self, state_prev: torch.Tensor, states: torch.Tensor, subtasks, weights=None, n: int = 1,
+                 counts: Optional[torch.Tensor] = None, events: Optional[torch.Tensor] = None,
+                 reward: Optional[torch.Tensor] = None):
+        """Subtask progress (oc_progress) of n consecutive states `states` (one state, or an
+        oc_step_n trajectory whose state_in is `state_prev`): per step and env the goal-object
+        count of every subtask (RealAgent.def_subtask_completion's cur_obj_count), the completion
+        events against the state before (is_subtask_complete; bit b of plane c is subtask 8c + b)
+        and reward = the sum of `weights` (None: 1.0 each) over the set events.  `subtasks` are
+        oc_subtask rows (capi.progress_subtasks makes them from recipe subtasks); only kind and
+        goal_mask are read.  Given some outputs only those are computed; given none, all three
+        are allocated.  Returns (counts, events, reward)."""
+        if counts is None and events is None and reward is None:
+            counts, events, reward = self.new_progress_buffers(len(subtasks), n)
+        self.progress_launcher(state_prev, states, subtasks, weights, n, counts, events, reward)()
+        return counts, events, reward
+
+    def progress_launcher(self, state_prev: torch.Tensor, states: torch.Tensor, subtasks, weights, n: int,
+                          counts: Optional[torch.Tensor], events: Optional[torch.Tensor],
+                          reward: Optional[torch.Tensor]):
+        """An oc_progress call bound once (see rollout_launcher)."""
+        S = len(subtasks)
+        self._check(state_prev, self.layout.state_bytes)
+        self._check(states, n * self.layout.state_bytes)
+        if counts is not None:
+            self._check(counts, n * S * self.pitch)
+        if events is not None:
+            self._check(events, n * capi.event_planes(S) * self.pitch)
+        if reward is not None:
+            self._check(reward, 4 * n * self.pitch, (torch.float32,))
+        args = (self._h, _ptr(state_prev), _ptr(states), int(n), capi.subtask_array(subtasks), S,
+                capi.weight_array(weights, S), _ptr(counts), _ptr(events), _ptr(reward), self.B, self._stream())
+        return _bound(self.lib.oc_progress, args)
+
     def set_likelihood_form(self, form: int) -> None:
         """oc_set_likelihood_form: capi.OC_LIK_FORM_AUTO (default) or OC_LIK_FORM_GROUPED (the
         grouped likelihood kernel on any level; the same outputs, for its parity test)."""
@@ -419,3 +460,21 @@ class CpuStepper:
                                            capi.OC_OBS_F16 if dt == np.float16 else capi.OC_OBS_U8, int(view_agent),
                                            self.B, self.nthreads))
         return obs, mask
+
+    def progress(self, state_prev: np.ndarray, states: np.ndarray, subtasks, weights=None, n: int = 1,
+                 want=("counts", "events", "reward")):
+        """oc_cpu_progress: (counts u8 [n, S, pitch], events u8 [n, planes, pitch], reward f32
+        [n, pitch]) of n consecutive host states against the state before; mirrors
+        OvercookedBatch.progress.  Outputs not named in `want` are None; columns past B stay zero."""
+        S, P = len(subtasks), self.pitch
+        for a, k in ((state_prev, 1), (states, n)):
+            if a.dtype != np.uint8 or not a.flags.c_contiguous or a.nbytes < k * self.layout.state_bytes:
+                raise ValueError("host buffers: contiguous uint8 of at least %d bytes" % (k * self.layout.state_bytes))
+        counts = np.zeros((n, S, P), np.uint8) if "counts" in want else None
+        events = np.zeros((n, capi.event_planes(S), P), np.uint8) if "events" in want else None
+        reward = np.zeros((n, P), np.float32) if "reward" in want else None
+        p = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        capi.check(self.lib.oc_cpu_progress(self._h, state_prev.ctypes.data, states.ctypes.data, int(n),
+                                            capi.subtask_array(subtasks), S, capi.weight_array(weights, S),
+                                            p(counts), p(events), p(reward), self.B, self.nthreads))
+        return counts, events, reward

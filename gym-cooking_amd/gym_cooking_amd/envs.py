@@ -793,6 +793,12 @@ class OvercookedVecEnv:
     ``uint8 [A, B]`` (bit k: ``World.NAV_ACTIONS[k]`` is in the reference's
     ``get_single_actions``; bit 4, the no-op, always).  Both reuse their buffers between calls
     (oc_observe); ``render()`` gives the reference's 560x560 image instead, at 1,600 times the bytes.
+
+    ``subtasks`` is ``recipes.all_subtasks(level)`` (the reference env's ``all_subtasks``), and
+    ``progress(weights)`` gives, for the last ``step()``, the goal-object count of each of them per
+    env (``RealAgent.def_subtask_completion``), the completion events of the step
+    (``is_subtask_complete``; bit b of plane c is subtask 8c + b) and a shaped reward, the sum
+    of ``weights`` over the events (oc_progress).  It is opt-in: ``step()`` does not compute it.
     """
 
     def __init__(self, level, num_agents: int, num_envs: int, max_num_timesteps: int = 100, device="cuda:0"):
@@ -805,16 +811,26 @@ class OvercookedVecEnv:
         self.ex, self.coll = self.batch.new_exec(), self.batch.new_coll()
         self.stats = self.batch.new_stats()
         self._fl = self.batch.layout.plane_flags
+        self._stepped = False  # progress(): whether the other ping-pong buffer is the state before
 
     @property
     def state(self) -> torch.Tensor:
         return self._s[self._i]
+
+    @property
+    def subtasks(self):
+        """recipes.all_subtasks(level): the order names the bits of progress()'s events."""
+        if getattr(self, "_subtasks", None) is None:
+            self._subtasks = _recipes.all_subtasks(self.batch.level)
+            self._sub_rows = capi.progress_subtasks(self._subtasks, self.batch.level.encoding)
+        return self._subtasks
 
     def planes(self) -> Dict[str, torch.Tensor]:
         return self.batch.planes(self.state)
 
     def reset(self) -> torch.Tensor:
         self.batch.reset(self.state)
+        self._stepped = False
         return self.state
 
     def step(self, actions: torch.Tensor):
@@ -827,6 +843,7 @@ class OvercookedVecEnv:
         src, dst = self._s[self._i], self._s[self._i ^ 1]
         self.batch.step(src, dst, act, self.ex, self.coll, self.stats)
         self._i ^= 1
+        self._stepped = True
         fl = dst.view(-1, P)[self._fl, :B]
         done = (fl & FLAG_DONE) != 0
         reward = ((fl & FLAG_SUCCESS) != 0).to(torch.int8)
@@ -859,6 +876,22 @@ class OvercookedVecEnv:
             self._mask = self.batch.new_action_mask()
         self.batch.observe(self.state, action_mask=self._mask)
         return self._mask.view(self.A, self.P)[:, :self.num_envs]
+
+    def progress(self, weights=None) -> Dict[str, torch.Tensor]:
+        """Subtask progress of the last step() (oc_progress over the two ping-pong buffers):
+        {"counts": u8 [S, B], "events": u8 [planes, B], "reward": f32 [B]} for S = len(subtasks).
+        Before the first step (and after reset()) the state is compared with itself: no events,
+        valid counts.  Views of this env's buffers, rewritten by the next call."""
+        S = len(self.subtasks)
+        if S == 0:
+            raise ValueError("the level's recipes have no subtasks")
+        if getattr(self, "_prog", None) is None:
+            self._prog = self.batch.new_progress_buffers(S)
+        prev = self._s[self._i ^ 1] if self._stepped else self.state
+        c, e, r = self._prog
+        self.batch.progress(prev, self.state, self._sub_rows, weights, 1, c, e, r)
+        B = self.num_envs
+        return {"counts": c[0, :, :B], "events": e[0, :, :B], "reward": r[0, :B]}
 
     def episode_stats(self) -> torch.Tensor:
         """int64 [episodes, successes, steps, collisions, errors] since construction."""

@@ -13,6 +13,8 @@
  *                               (:767-770, gym_cooking/utils/interact.py:4-89) + done/reward (:316-376)
  *   oc_observe, oc_cpu_observe <- a grid encoding of world.objects / sim_agents (utils/core.py:28-305) and
  *                               get_single_actions (gym_cooking/navigation_planner/utils.py:55-90) per agent
+ *   oc_progress, oc_cpu_progress <- RealAgent.def_subtask_completion / is_subtask_complete
+ *                               (gym_cooking/utils/agent.py:286-368) for every subtask of a recipe, per env
  *   oc_gen_actions           <- synthetic action streams (the reference env has no RNG)
  *   oc_stats_*               <- the per-episode bookkeeping main.py keeps in its metrics Bag
  *                               (gym_cooking/misc/metrics/metrics_bag.py:40-72), reduced per GPU
@@ -43,7 +45,7 @@
 extern "C" {
 #endif
 
-#define OC_ABI_VERSION 11
+#define OC_ABI_VERSION 12
 
 #define OC_MAX_AGENTS 4
 #define OC_MAX_ITEMS 16  /* item slots: K = 4, 8 or 16 per level */
@@ -493,6 +495,66 @@ int oc_observe(const oc_handle* h, const void* state, void* obs, uint8_t* action
  * written.  It never touches the device; oc_observe never calls it. */
 int oc_cpu_observe(const oc_handle* h, const void* state, void* obs, uint8_t* action_mask,
                    int32_t dtype, int32_t view_agent, int64_t B, int32_t nthreads);
+
+/* ---------------------------------------------------------------------------------------
+ * Subtask progress (ABI 12): per env and per subtask the reference agent's goal-object count,
+ * the completion events of a transition and a shaped reward.  A trainer's dense signal, a
+ * delegator's incomplete_subtasks test, the goal_count of an oc_rollout configuration.
+ *
+ * Of a subtask only `kind` and `goal_mask` are read (the other fields are ignored, as
+ * oc_subtask_bounds ignores goal_count).  count_i(s), u8, of a state s:
+ *   A slot is live when its cell is not OC_LOC_DEAD / OC_LOC_DEAD16.  Its cell is the item's
+ *   cell; for a held item (a live slot some agent's hold plane names; the lowest such agent)
+ *   that is its holder's square y * W + x, as the reference's held object carries its holder's
+ *   location (SimAgent.acquire / move_to, utils/agent.py:408-423).  States the engine or the
+ *   oracle made keep the item cell on the holder already; the count does not rely on it.
+ *   OC_SUB_CHOP, OC_SUB_MERGE : the number of distinct cells of live slots whose mask byte equals
+ *       goal_mask = len(world.get_all_object_locs(goal_obj)), a list(set(...)) of locations
+ *       (utils/world.py:354-387; agent.py:286-353), in either mask encoding (byte equality)
+ *   OC_SUB_DELIVER : the number of live slots, not held, with mask == goal_mask on any Delivery
+ *       square: the reference takes a list here, not a set (agent.py:354-361), so two equal
+ *       dishes on one Delivery square count twice
+ *   OC_SUB_NONE : 0
+ * Per step r of a call, prev = states[r-1] (state_prev for r = 0), cur = states[r]:
+ *   counts[r][i][e] = count_i(cur)
+ *   event i         = prev does not carry OC_FLAG_DONE and count_i(cur) > count_i(prev): exactly
+ *       is_subtask_complete(cur.world) (agent.py:363-368) of an agent whose
+ *       def_subtask_completion ran on prev.  An env that was DONE at prev is the auto-reset
+ *       template in cur and reports no event (build-defined, like auto-reset itself); a step that
+ *       ends in ERR leaves the state unchanged and so reports none; the delivering step that
+ *       sets DONE and SUCCESS does report its Deliver event.
+ *   events[r][c][e], u8 : bit b of plane c is subtask 8c + b; OC_PROGRESS_EVENT_PLANES(n) planes
+ *   reward[r][e], f32   : from +0.0f, + weights[i] for every set event in ascending i, plain f32
+ *       adds in that order (weights NULL: all 1.0f, the number of events)
+ * ------------------------------------------------------------------------------------- */
+#define OC_PROGRESS_EVENT_PLANES(n) (((n) + 7) / 8)
+
+/*   state_prev : the state before states[0] (oc_layout), device memory
+ *   states     : n >= 1 consecutive layout buffers, state_bytes apart: one state (n = 1), or an
+ *                oc_step_n trajectory with state_prev the launch's state_in
+ *   subtasks   : host array of num_subtasks (1..OC_MAX_SUBTASKS); kinds OC_SUB_*
+ *   weights    : host array of num_subtasks floats, or NULL (all 1.0f)
+ *   counts     : nullable; n x u8 [num_subtasks][pitch]
+ *   events     : nullable; n x u8 [OC_PROGRESS_EVENT_PLANES(num_subtasks)][pitch]
+ *   reward     : nullable; n x f32 [pitch], 16-byte aligned
+ * Inputs are read-only and may alias each other (state_prev == states: no events, valid counts).
+ * Columns past B as exec_actions: the batch's last 4-env word may be completed with zeros (for
+ * reward the floats up to the next multiple of 4 above B); nothing at or past that is written.
+ * A bad n, num_subtasks or kind, all three outputs NULL, or a host-only handle is OC_EINVAL.
+ * Stream-ordered, no allocation, no synchronisation (hipGraph-capturable, as oc_step).  One
+ * launch whatever n: every offset inside it is 64-bit, and each state is loaded once (step r's
+ * cur is step r + 1's prev). */
+int oc_progress(const oc_handle* h, const void* state_prev, const void* states, int32_t n,
+                const oc_subtask* subtasks, int32_t num_subtasks, const float* weights,
+                uint8_t* counts, uint8_t* events, float* reward, int64_t B, void* stream);
+
+/* The same on the host (what oc_cpu_step is to oc_step): HOST buffers, works on OC_DEVICE_HOST
+ * handles, the kernel's count and event functions compiled for the host, threaded over env
+ * ranges (nthreads 0 = the host's hardware threads; at least 16 Ki envs each).  Nothing past
+ * column B is written.  It never touches the device; oc_progress never calls it. */
+int oc_cpu_progress(const oc_handle* h, const void* state_prev, const void* states, int32_t n,
+                    const oc_subtask* subtasks, int32_t num_subtasks, const float* weights,
+                    uint8_t* counts, uint8_t* events, float* reward, int64_t B, int32_t nthreads);
 
 #ifdef __cplusplus
 }
