@@ -31,15 +31,19 @@
 #include <exception>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/oc_engine.h"
+#include "oc_layout.h"
 #include "oc_observe.h"
 #include "oc_progress.h"
 #include "oc_rollout.h"
 #include "oc_swar.h"
 
 namespace {
+
+using ocly::Planes;  // the state's plane layout (oc_layout.h)
 
 constexpr int kBlock = 256;  // 4 waves
 constexpr int kStepBlock = 128;  // oc_step_kernel: 2 waves
@@ -127,23 +131,23 @@ __device__ __forceinline__ void bst32(__amdgpu_buffer_rsrc_t r, uint32_t v, uint
 
 template <int A, int K, bool kActs = true>
 __device__ __forceinline__ void load_chunk(Chunk<A, K>& c, const Bufs& b, uint32_t P, uint32_t g) {
-    constexpr int kPY = A, kPH = 2 * A, kPL = 3 * A, kPM = 3 * A + K, kPT = 3 * A + 2 * K, kPF = kPT + 2;
+    using PL = Planes<A, K, false>;
     const uint32_t vo = g * 4u;
 #pragma unroll
     for (int a = 0; a < A; ++a) {
         c.wx[a] = bld32(b.sin, vo, a * P);
-        c.wy[a] = bld32(b.sin, vo, (kPY + a) * P);
-        c.wh[a] = bld32(b.sin, vo, (kPH + a) * P);
+        c.wy[a] = bld32(b.sin, vo, (PL::Y + a) * P);
+        c.wh[a] = bld32(b.sin, vo, (PL::HOLD + a) * P);
         if (kActs) c.wa[a] = bld32(b.act, vo, a * P);
     }
 #pragma unroll
     for (int j = 0; j < K; ++j) {
-        c.wl[j] = bld32(b.sin, vo, (kPL + j) * P);
-        c.wm[j] = bld32(b.sin, vo, (kPM + j) * P);
+        c.wl[j] = bld32(b.sin, vo, (PL::LOC + j) * P);
+        c.wm[j] = bld32(b.sin, vo, (PL::MASK + j) * P);
     }
-    const auto t = __builtin_amdgcn_raw_buffer_load_b64(b.sin, (int)(g * 8u), (int)(kPT * P), 0);
+    const auto t = __builtin_amdgcn_raw_buffer_load_b64(b.sin, (int)(g * 8u), (int)(PL::T * P), 0);
     c.wt = make_uint2(t[0], t[1]);
-    c.wf = bld32(b.sin, vo, kPF * P);
+    c.wf = bld32(b.sin, vo, PL::F * P);
 }
 
 // Per-lane episode counters; at the end of the kernel a wave sums them and lane 0 adds them
@@ -156,7 +160,7 @@ struct StepStats {
 template <int A, int K, int CP = 0, int MODE = 1>
 __device__ __forceinline__ void step_chunk(const LevelArgs& L, const uint8_t* tbl, Chunk<A, K>& c, const Bufs& b,
                                            bool has_ex, bool has_coll, uint32_t P, uint32_t g, StepStats& st) {
-    constexpr int kPY = A, kPH = 2 * A, kPL = 3 * A, kPM = 3 * A + K, kPT = 3 * A + 2 * K, kPF = kPT + 2;
+    using PL = Planes<A, K, false>;
     auto cls_of = [tbl](uint32_t cells) -> uint32_t {
         const uint32_t b0 = tbl[cells & 0xFFu], b1 = tbl[(cells >> 8) & 0xFFu], b2 = tbl[(cells >> 16) & 0xFFu],
                        b3 = tbl[cells >> 24];
@@ -189,18 +193,18 @@ __device__ __forceinline__ void step_chunk(const LevelArgs& L, const uint8_t* tb
 #pragma unroll
     for (int a = 0; a < A; ++a) {
         bst32<CP>(b.sout, c.wx[a], vo, a * P);
-        bst32<CP>(b.sout, c.wy[a], vo, (kPY + a) * P);
-        bst32<CP>(b.sout, c.wh[a], vo, (kPH + a) * P);
+        bst32<CP>(b.sout, c.wy[a], vo, (PL::Y + a) * P);
+        bst32<CP>(b.sout, c.wh[a], vo, (PL::HOLD + a) * P);
     }
 #pragma unroll
     for (int j = 0; j < K; ++j) {
-        bst32<CP>(b.sout, c.wl[j], vo, (kPL + j) * P);
-        bst32<CP>(b.sout, c.wm[j], vo, (kPM + j) * P);
+        bst32<CP>(b.sout, c.wl[j], vo, (PL::LOC + j) * P);
+        bst32<CP>(b.sout, c.wm[j], vo, (PL::MASK + j) * P);
     }
     typedef unsigned int u32x2 __attribute__((__vector_size__(2 * sizeof(unsigned int))));
     const u32x2 tw = {T0, T1};
-    __builtin_amdgcn_raw_buffer_store_b64(tw, b.sout, (int)(g * 8u), (int)(kPT * P), CP);
-    bst32<CP>(b.sout, c.wf, vo, kPF * P);
+    __builtin_amdgcn_raw_buffer_store_b64(tw, b.sout, (int)(g * 8u), (int)(PL::T * P), CP);
+    bst32<CP>(b.sout, c.wf, vo, PL::F * P);
     if (has_ex) {
 #pragma unroll
         for (int a = 0; a < A; ++a) bst32<CP>(b.ex, ex[a], vo, a * P);
@@ -224,7 +228,7 @@ __global__ __launch_bounds__(kStepBlock) void oc_step_kernel(LevelArgs L, const 
                                                              uint8_t* __restrict__ coll_out,
                                                              uint64_t* __restrict__ stats, uint32_t stat_rows) {
     const uint32_t P = (uint32_t)L.pitch;  // state <= 2 GiB (checked on the host)
-    constexpr int NP = 3 * A + 2 * K + 3;
+    constexpr int NP = Planes<A, K, false>::NP;
     Bufs b;
     b.sin = make_rsrc(sin, (int64_t)NP * P);
     b.sout = make_rsrc(sout, (int64_t)NP * P);
@@ -336,8 +340,8 @@ __global__ __launch_bounds__(kBlock + (LW ? 64 : 0), LW ? 5 : 1) void oc_step_n_
     const uint32_t lane = threadIdx.x & 63u;
     const uint8_t* tbl = (const uint8_t*)tbl4;
     const uint32_t P = (uint32_t)L.pitch, nlanes = P / kEPL, stride = gridDim.x * (uint32_t)kBlock;
-    constexpr int NP = 3 * A + 2 * K + 3;
-    constexpr int kPY = A, kPH = 2 * A, kPL = 3 * A, kPM = 3 * A + K, kPT = 3 * A + 2 * K, kPF = kPT + 2;
+    using PL = Planes<A, K, false>;
+    constexpr int NP = PL::NP;
     auto cls_of = [&](uint32_t cells) -> uint32_t {
         const uint32_t b0 = tbl[cells & 0xFFu], b1 = tbl[(cells >> 8) & 0xFFu], b2 = tbl[(cells >> 16) & 0xFFu],
                        b3 = tbl[cells >> 24];
@@ -442,17 +446,17 @@ __global__ __launch_bounds__(kBlock + (LW ? 64 : 0), LW ? 5 : 1) void oc_step_n_
 #pragma unroll
             for (int a = 0; a < A; ++a) {
                 bst32<CP>(tr, c.wx[a], vo, base + a * P);
-                bst32<CP>(tr, c.wy[a], vo, base + (kPY + a) * P);
-                bst32<CP>(tr, c.wh[a], vo, base + (kPH + a) * P);
+                bst32<CP>(tr, c.wy[a], vo, base + (PL::Y + a) * P);
+                bst32<CP>(tr, c.wh[a], vo, base + (PL::HOLD + a) * P);
             }
 #pragma unroll
             for (int j = 0; j < K; ++j) {
-                bst32<CP>(tr, c.wl[j], vo, base + (kPL + j) * P);
-                bst32<CP>(tr, c.wm[j], vo, base + (kPM + j) * P);
+                bst32<CP>(tr, c.wl[j], vo, base + (PL::LOC + j) * P);
+                bst32<CP>(tr, c.wm[j], vo, base + (PL::MASK + j) * P);
             }
             const u32x2 tw = {T0, T1};
-            __builtin_amdgcn_raw_buffer_store_b64(tw, tr, (int)(g * 8u), (int)(base + kPT * P), CP);
-            bst32<CP>(tr, c.wf, vo, base + kPF * P);
+            __builtin_amdgcn_raw_buffer_store_b64(tw, tr, (int)(g * 8u), (int)(base + PL::T * P), CP);
+            bst32<CP>(tr, c.wf, vo, base + PL::F * P);
 #pragma unroll
             for (int a = 0; a < A; ++a) bst32<CP>(b.ex, ex[a], vo, (uint32_t)(r * A + a) * P);
             bst32<CP>(b.coll, cm, vo, (uint32_t)r * P);
@@ -461,17 +465,17 @@ __global__ __launch_bounds__(kBlock + (LW ? 64 : 0), LW ? 5 : 1) void oc_step_n_
 #pragma unroll
         for (int a = 0; a < A; ++a) {
             bst32<CP>(b.sout, c.wx[a], vo, a * P);
-            bst32<CP>(b.sout, c.wy[a], vo, (kPY + a) * P);
-            bst32<CP>(b.sout, c.wh[a], vo, (kPH + a) * P);
+            bst32<CP>(b.sout, c.wy[a], vo, (PL::Y + a) * P);
+            bst32<CP>(b.sout, c.wh[a], vo, (PL::HOLD + a) * P);
         }
 #pragma unroll
         for (int j = 0; j < K; ++j) {
-            bst32<CP>(b.sout, c.wl[j], vo, (kPL + j) * P);
-            bst32<CP>(b.sout, c.wm[j], vo, (kPM + j) * P);
+            bst32<CP>(b.sout, c.wl[j], vo, (PL::LOC + j) * P);
+            bst32<CP>(b.sout, c.wm[j], vo, (PL::MASK + j) * P);
         }
         const u32x2 tw = {T0, T1};
-        __builtin_amdgcn_raw_buffer_store_b64(tw, b.sout, (int)(g * 8u), (int)(kPT * P), CP);
-        bst32<CP>(b.sout, c.wf, vo, kPF * P);
+        __builtin_amdgcn_raw_buffer_store_b64(tw, b.sout, (int)(g * 8u), (int)(PL::T * P), CP);
+        bst32<CP>(b.sout, c.wf, vo, PL::F * P);
     }
     if (loader) return;  // the stepping waves count and fold the statistics
     if (stats != nullptr) {
@@ -576,14 +580,6 @@ __device__ __forceinline__ void stage_roll_tables(const RollArgs& R, const uint8
     __syncthreads();
 }
 
-// Plane indices of the state layout (oc_get_layout): a wide level (u16 cells) has its item
-// cells' high bytes in K planes after the low ones.
-template <int A, int K, bool W>
-struct Planes {
-    static constexpr int X = 0, Y = A, H = 2 * A, L = 3 * A, LH = 3 * A + K, M = 3 * A + (W ? 2 : 1) * K;
-    static constexpr int T = M + K, F = T + 2, NP = F + 1;
-};
-
 template <int A, int K, bool W = false>
 __device__ __forceinline__ ocro::RowT<K, W> load_row(const uint8_t* __restrict__ sin, int64_t P, int64_t e) {
     using PL = Planes<A, K, W>;
@@ -593,14 +589,14 @@ __device__ __forceinline__ ocro::RowT<K, W> load_row(const uint8_t* __restrict__
     for (int a = 0; a < A; ++a) {
         r.x |= (uint32_t)sin[a * P + e] << (8 * a);
         r.y |= (uint32_t)sin[(PL::Y + a) * P + e] << (8 * a);
-        r.h |= (uint32_t)sin[(PL::H + a) * P + e] << (8 * a);
+        r.h |= (uint32_t)sin[(PL::HOLD + a) * P + e] << (8 * a);
     }
 #pragma unroll
     for (int j = 0; j < K; ++j) {
-        uint64_t c = sin[(PL::L + j) * P + e];
-        if (W) c |= (uint64_t)sin[(PL::LH + j) * P + e] << 8;
+        uint64_t c = sin[(PL::LOC + j) * P + e];
+        if (W) c |= (uint64_t)sin[(PL::LOC_HI + j) * P + e] << 8;
         r.loc[j / Row::LPW] |= c << (Row::kLocBits * (j % Row::LPW));
-        r.mask[j >> 3] |= (uint64_t)sin[(PL::M + j) * P + e] << (8 * (j & 7));
+        r.mask[j >> 3] |= (uint64_t)sin[(PL::MASK + j) * P + e] << (8 * (j & 7));
     }
     return r;
 }
@@ -619,14 +615,14 @@ __device__ __forceinline__ void store_row(uint8_t* __restrict__ sout, int64_t P,
     for (int a = 0; a < A; ++a) {
         st(a * P + e, (uint32_t)r.ax(a));
         st((PL::Y + a) * P + e, (uint32_t)r.ay(a));
-        st((PL::H + a) * P + e, (uint32_t)r.ah(a));
+        st((PL::HOLD + a) * P + e, (uint32_t)r.ah(a));
     }
 #pragma unroll
     for (int j = 0; j < K; ++j) {
         const uint32_t c = (uint32_t)r.il(j);
-        st((PL::L + j) * P + e, c);
-        if (W) st((PL::LH + j) * P + e, c >> 8);
-        st((PL::M + j) * P + e, (uint32_t)r.im(j));
+        st((PL::LOC + j) * P + e, c);
+        if (W) st((PL::LOC_HI + j) * P + e, c >> 8);
+        st((PL::MASK + j) * P + e, (uint32_t)r.im(j));
     }
 }
 
@@ -1343,14 +1339,14 @@ __global__ __launch_bounds__(kBlock) void oc_step_wide_kernel(WideArgs R, const 
         for (int a = 0; a < A; ++a) {
             X[a] = bld32(rs, vo, a * P);
             Y[a] = bld32(rs, vo, (PL::Y + a) * P);
-            H[a] = bld32(rs, vo, (PL::H + a) * P);
+            H[a] = bld32(rs, vo, (PL::HOLD + a) * P);
             wa[a] = bld32(ra, vo, a * P);
         }
 #pragma unroll
         for (int j = 0; j < K; ++j) {
-            LO[j] = bld32(rs, vo, (PL::L + j) * P);
-            HI[j] = bld32(rs, vo, (PL::LH + j) * P);
-            M[j] = bld32(rs, vo, (PL::M + j) * P);
+            LO[j] = bld32(rs, vo, (PL::LOC + j) * P);
+            HI[j] = bld32(rs, vo, (PL::LOC_HI + j) * P);
+            M[j] = bld32(rs, vo, (PL::MASK + j) * P);
         }
         const auto tw0 = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)(g * 8u), (int)(PL::T * P), 0);
         uint32_t T0 = tw0[0], T1 = tw0[1], F = bld32(rs, vo, PL::F * P);
@@ -1380,14 +1376,14 @@ __global__ __launch_bounds__(kBlock) void oc_step_wide_kernel(WideArgs R, const 
             for (int a = 0; a < A; ++a) {
                 bst32<kCPnt>(rt, X[a], vo, base + a * P);
                 bst32<kCPnt>(rt, Y[a], vo, base + (PL::Y + a) * P);
-                bst32<kCPnt>(rt, H[a], vo, base + (PL::H + a) * P);
+                bst32<kCPnt>(rt, H[a], vo, base + (PL::HOLD + a) * P);
                 bst32<kCPnt>(rx, EX[a], vo, (uint32_t)(q * A + a) * P);
             }
 #pragma unroll
             for (int j = 0; j < K; ++j) {
-                bst32<kCPnt>(rt, LO[j], vo, base + (PL::L + j) * P);
-                bst32<kCPnt>(rt, HI[j], vo, base + (PL::LH + j) * P);
-                bst32<kCPnt>(rt, M[j], vo, base + (PL::M + j) * P);
+                bst32<kCPnt>(rt, LO[j], vo, base + (PL::LOC + j) * P);
+                bst32<kCPnt>(rt, HI[j], vo, base + (PL::LOC_HI + j) * P);
+                bst32<kCPnt>(rt, M[j], vo, base + (PL::MASK + j) * P);
             }
             const u32x2 tv = {T0, T1};
             __builtin_amdgcn_raw_buffer_store_b64(tv, rt, (int)(g * 8u), (int)(base + PL::T * P), kCPnt);
@@ -1400,13 +1396,13 @@ __global__ __launch_bounds__(kBlock) void oc_step_wide_kernel(WideArgs R, const 
         for (int a = 0; a < A; ++a) {
             bst32<kCPnt>(ro, X[a], vo, a * P);
             bst32<kCPnt>(ro, Y[a], vo, (PL::Y + a) * P);
-            bst32<kCPnt>(ro, H[a], vo, (PL::H + a) * P);
+            bst32<kCPnt>(ro, H[a], vo, (PL::HOLD + a) * P);
         }
 #pragma unroll
         for (int j = 0; j < K; ++j) {
-            bst32<kCPnt>(ro, LO[j], vo, (PL::L + j) * P);
-            bst32<kCPnt>(ro, HI[j], vo, (PL::LH + j) * P);
-            bst32<kCPnt>(ro, M[j], vo, (PL::M + j) * P);
+            bst32<kCPnt>(ro, LO[j], vo, (PL::LOC + j) * P);
+            bst32<kCPnt>(ro, HI[j], vo, (PL::LOC_HI + j) * P);
+            bst32<kCPnt>(ro, M[j], vo, (PL::MASK + j) * P);
         }
         const u32x2 tv = {T0, T1};
         __builtin_amdgcn_raw_buffer_store_b64(tv, ro, (int)(g * 8u), (int)(PL::T * P), kCPnt);
@@ -1434,13 +1430,13 @@ __global__ __launch_bounds__(kBlock) void oc_reset_wide_kernel(WideArgs R, uint8
     for (int a = 0; a < A; ++a) {
         s[a * P + e] = R.S.spawn_x[a];
         s[(PL::Y + a) * P + e] = R.S.spawn_y[a];
-        s[(PL::H + a) * P + e] = (uint8_t)OC_HOLD_NONE;
+        s[(PL::HOLD + a) * P + e] = (uint8_t)OC_HOLD_NONE;
     }
 #pragma unroll
     for (int j = 0; j < K; ++j) {
-        s[(PL::L + j) * P + e] = (uint8_t)R.S.item_cell[j];
-        s[(PL::LH + j) * P + e] = (uint8_t)(R.S.item_cell[j] >> 8);
-        s[(PL::M + j) * P + e] = R.S.item_mask[j];
+        s[(PL::LOC + j) * P + e] = (uint8_t)R.S.item_cell[j];
+        s[(PL::LOC_HI + j) * P + e] = (uint8_t)(R.S.item_cell[j] >> 8);
+        s[(PL::MASK + j) * P + e] = R.S.item_mask[j];
     }
     ((uint16_t*)(s + PL::T * P))[e] = 0;
     s[PL::F * P + e] = 0;
@@ -1517,7 +1513,7 @@ __global__ __launch_bounds__(kBlock) void oc_render_kernel(RenderArgs R, const u
     const int ty = (int)(strip % (uint32_t)R.H);
     const int W = R.W, tile = R.tile;
     // planes: a wide level's item cells are u16, low bytes then high bytes, before the masks
-    constexpr int kPX = 0, kPY = A, kPH = 2 * A, kPL = 3 * A, kPLH = 3 * A + K, kPM = 3 * A + (WIDE ? 2 : 1) * K;
+    using PL = Planes<A, K, WIDE>;
     // The cell row's draw list: every column lane counts its draws, a block prefix sum places
     // them, and the lanes write them in the same order (draw order within a column).
     const int tx = (int)threadIdx.x, cell = ty * W + tx;
@@ -1527,7 +1523,7 @@ __global__ __launch_bounds__(kBlock) void oc_render_kernel(RenderArgs R, const u
         uint32_t held = 0u;
 #pragma unroll
         for (int a = 0; a < A; ++a) {
-            const uint32_t h = s[(kPH + a) * P];
+            const uint32_t h = s[(PL::HOLD + a) * P];
             if (h < (uint32_t)K) held |= 1u << h;
         }
         auto push = [&](int32_t off, int cls) {
@@ -1556,7 +1552,7 @@ __global__ __launch_bounds__(kBlock) void oc_render_kernel(RenderArgs R, const u
         uint32_t here = 0u;
 #pragma unroll
         for (int j = 0; j < K; ++j) {
-            const int c = WIDE ? (int)s[(kPL + j) * P] | (int)s[(kPLH + j) * P] << 8 : (int)s[(kPL + j) * P];
+            const int c = WIDE ? (int)s[(PL::LOC + j) * P] | (int)s[(PL::LOC_HI + j) * P] << 8 : (int)s[(PL::LOC + j) * P];
             if (c == cell) here |= 1u << j;  // a dead slot (0xFF / 0xFFFF) is no cell
         }
         here &= ~held;
@@ -1572,15 +1568,15 @@ __global__ __launch_bounds__(kBlock) void oc_render_kernel(RenderArgs R, const u
                 j = (int)(best & 31u);
             }
             here &= ~(1u << j);
-            push_item(s[(kPM + j) * P], 0, 1, 0);
+            push_item(s[(PL::MASK + j) * P], 0, 1, 0);
         }
         // ... then the agents in order, each with its held object (draw_agent / draw_agent_object, :98-136)
 #pragma unroll
         for (int a = 0; a < A; ++a) {
-            if ((int)s[(kPY + a) * P] * W + (int)s[(kPX + a) * P] != cell) continue;
+            if ((int)s[(PL::Y + a) * P] * W + (int)s[(PL::X + a) * P] != cell) continue;
             push(R.agent_off[a], 0);
-            const uint32_t h = s[(kPH + a) * P];
-            if (h < (uint32_t)K) push_item(s[(kPM + h) * P], 2, 3, 1);
+            const uint32_t h = s[(PL::HOLD + a) * P];
+            if (h < (uint32_t)K) push_item(s[(PL::MASK + h) * P], 2, 3, 1);
         }
         return n;
     };
@@ -1722,19 +1718,20 @@ __global__ __launch_bounds__(kBlock) void oc_reset_kernel(LevelArgs L, uint8_t* 
     const int64_t e0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * kEPL;
     auto rep = [](uint32_t b) { return (b & 0xFFu) * 0x01010101u; };
     auto st32 = [&](int plane, uint32_t v) { *reinterpret_cast<uint32_t*>(s + plane * P + e0) = v; };
+    using PL = Planes<A, K, false>;
 #pragma unroll
     for (int a = 0; a < A; ++a) {
-        st32(a, rep(byte_of(L.tmpl_x, a)));
-        st32(A + a, rep(byte_of(L.tmpl_y, a)));
-        st32(2 * A + a, rep(OC_HOLD_NONE));
+        st32(PL::X + a, rep(byte_of(L.tmpl_x, a)));
+        st32(PL::Y + a, rep(byte_of(L.tmpl_y, a)));
+        st32(PL::HOLD + a, rep(OC_HOLD_NONE));
     }
 #pragma unroll
     for (int j = 0; j < K; ++j) {
-        st32(3 * A + j, rep(byte_of4(L.tmpl_cell, j)));
-        st32(3 * A + K + j, rep(byte_of4(L.tmpl_mask, j)));
+        st32(PL::LOC + j, rep(byte_of4(L.tmpl_cell, j)));
+        st32(PL::MASK + j, rep(byte_of4(L.tmpl_mask, j)));
     }
-    *reinterpret_cast<uint2*>(s + (3 * A + 2 * K) * P + 2 * e0) = make_uint2(0u, 0u);
-    st32(3 * A + 2 * K + 2, 0u);
+    *reinterpret_cast<uint2*>(s + PL::T * P + 2 * e0) = make_uint2(0u, 0u);
+    st32(PL::F, 0u);
 }
 
 // Order-sensitive 64-bit checksum of the state of envs [0, B):
@@ -1890,78 +1887,91 @@ int64_t stats_rows(const oc_handle*, int64_t B) {
     return need < kStatRows ? need : kStatRows;
 }
 
+// The host step workers' plane word g (4 envs) of a plane, read and written whole.
+static uint32_t rd(const uint8_t* base, int64_t P, int plane, int64_t g) {
+    uint32_t v;
+    memcpy(&v, base + plane * P + 4 * g, 4);
+    return v;
+}
+static void wr(uint8_t* base, int64_t P, int plane, int64_t g, uint32_t v) { memcpy(base + plane * P + 4 * g, &v, 4); }
+
+// The host step workers' statistics: add() tallies one stepped word (its rem = B - 4g envs that
+// count), store() writes a range's row.
+struct HostTally {
+    uint64_t eps = 0, succ = 0, steps = 0, ncoll = 0, err = 0;
+    void add(int64_t rem, bool full, uint32_t f_in, uint32_t F, uint32_t T0, uint32_t T1, uint32_t CM) {
+        const uint32_t vmask = rem >= kEPL ? 0xFFFFFFFFu : (1u << (8 * (uint32_t)rem)) - 1u;
+        ncoll += (uint64_t)__builtin_popcount(CM & vmask);
+        if (!full) return;
+        const uint32_t ended = (F & ~f_in & vmask) & ocsw::k01;
+        for (int q = 0; q < kEPL; ++q) {
+            if (!((ended >> (8 * q)) & 1u)) continue;
+            ++eps;
+            succ += (F >> (8 * q + 1)) & 1u;
+            err += (F >> (8 * q + 2)) & 1u;
+            steps += ((q < 2 ? T0 : T1) >> (16 * (q & 1))) & 0xFFFFu;
+        }
+    }
+    void store(uint64_t* st) const {
+        st[OC_STAT_EPISODES] = eps;
+        st[OC_STAT_SUCCESSES] = succ;
+        st[OC_STAT_STEPS] = steps;
+        st[OC_STAT_COLLISIONS] = ncoll;
+        st[OC_STAT_ERRORS] = err;
+    }
+};
+
 // oc_cpu_step's worker: the host pass of the same SWAR step (oc_swar.h), words [g0, g1) of
 // the batch (4 envs each, as one lane of oc_step_kernel), per-word rare-event split.
 template <int A, int K, int MODE>
 static void cpu_step_words(const oc_handle* h, const uint8_t* sin, uint8_t* sout, const uint8_t* act,
                            uint8_t* exo, uint8_t* coll, int64_t B, int64_t P, int64_t g0, int64_t g1,
                            uint64_t* st) {
-    constexpr int kPY = A, kPH = 2 * A, kPL = 3 * A, kPM = 3 * A + K, kPT = 3 * A + 2 * K, kPF = kPT + 2;
+    using PL = Planes<A, K, false>;
     const LevelArgs& L = h->args;
     const uint8_t* tbl = (const uint8_t*)L.cls4;
     auto cls_of = [tbl](uint32_t c) -> uint32_t {
         return (uint32_t)tbl[c & 0xFFu] | ((uint32_t)tbl[(c >> 8) & 0xFFu] << 8) |
                ((uint32_t)tbl[(c >> 16) & 0xFFu] << 16) | ((uint32_t)tbl[c >> 24] << 24);
     };
-    auto rd = [P](const uint8_t* base, int plane, int64_t g) {
-        uint32_t v;
-        memcpy(&v, base + plane * P + 4 * g, 4);
-        return v;
-    };
-    auto wr = [P](uint8_t* base, int plane, int64_t g, uint32_t v) { memcpy(base + plane * P + 4 * g, &v, 4); };
-    uint64_t eps = 0, succ = 0, steps = 0, ncoll = 0, err = 0;
+    HostTally tally;
     for (int64_t g = g0; g < g1; ++g) {
         uint32_t X[A], Y[A], Hh[A], Lc[K], M[K], AC[A], EX[A], T0, T1, F, CM;
         for (int a = 0; a < A; ++a) {
-            X[a] = rd(sin, a, g);
-            Y[a] = rd(sin, kPY + a, g);
-            Hh[a] = rd(sin, kPH + a, g);
-            AC[a] = rd(act, a, g);
+            X[a] = rd(sin, P, a, g);
+            Y[a] = rd(sin, P, PL::Y + a, g);
+            Hh[a] = rd(sin, P, PL::HOLD + a, g);
+            AC[a] = rd(act, P, a, g);
         }
         for (int j = 0; j < K; ++j) {
-            Lc[j] = rd(sin, kPL + j, g);
-            M[j] = rd(sin, kPM + j, g);
+            Lc[j] = rd(sin, P, PL::LOC + j, g);
+            M[j] = rd(sin, P, PL::MASK + j, g);
         }
-        memcpy(&T0, sin + kPT * P + 8 * g, 4);
-        memcpy(&T1, sin + kPT * P + 8 * g + 4, 4);
-        F = rd(sin, kPF, g);
+        memcpy(&T0, sin + PL::T * P + 8 * g, 4);
+        memcpy(&T1, sin + PL::T * P + 8 * g + 4, 4);
+        F = rd(sin, P, PL::F, g);
         const uint32_t f_in = F;
         uint32_t pending = ocsw::at_done80<K, MODE>(L.sw, Lc);
         const bool full = ocsw::step4<A, K, MODE>(L.sw, X, Y, Hh, Lc, M, T0, T1, F, AC, EX, CM, cls_of,
                                                   [](uint32_t v) { return v != 0u; }, pending);
         const int64_t rem = B - g * kEPL;
-        const uint32_t vmask = rem >= kEPL ? 0xFFFFFFFFu : (1u << (8 * (uint32_t)rem)) - 1u;
-        ncoll += (uint64_t)__builtin_popcount(CM & vmask);
-        if (full) {
-            const uint32_t ended = (F & ~f_in & vmask) & ocsw::k01;
-            for (int q = 0; q < kEPL; ++q) {
-                if (!((ended >> (8 * q)) & 1u)) continue;
-                ++eps;
-                succ += (F >> (8 * q + 1)) & 1u;
-                err += (F >> (8 * q + 2)) & 1u;
-                steps += ((q < 2 ? T0 : T1) >> (16 * (q & 1))) & 0xFFFFu;
-            }
-        }
+        tally.add(rem, full, f_in, F, T0, T1, CM);
         for (int a = 0; a < A; ++a) {
-            wr(sout, a, g, X[a]);
-            wr(sout, kPY + a, g, Y[a]);
-            wr(sout, kPH + a, g, Hh[a]);
-            if (exo != nullptr) wr(exo, a, g, EX[a]);
+            wr(sout, P, a, g, X[a]);
+            wr(sout, P, PL::Y + a, g, Y[a]);
+            wr(sout, P, PL::HOLD + a, g, Hh[a]);
+            if (exo != nullptr) wr(exo, P, a, g, EX[a]);
         }
         for (int j = 0; j < K; ++j) {
-            wr(sout, kPL + j, g, Lc[j]);
-            wr(sout, kPM + j, g, M[j]);
+            wr(sout, P, PL::LOC + j, g, Lc[j]);
+            wr(sout, P, PL::MASK + j, g, M[j]);
         }
-        memcpy(sout + kPT * P + 8 * g, &T0, 4);
-        memcpy(sout + kPT * P + 8 * g + 4, &T1, 4);
-        wr(sout, kPF, g, F);
-        if (coll != nullptr) wr(coll, 0, g, CM);
+        memcpy(sout + PL::T * P + 8 * g, &T0, 4);
+        memcpy(sout + PL::T * P + 8 * g + 4, &T1, 4);
+        wr(sout, P, PL::F, g, F);
+        if (coll != nullptr) wr(coll, P, 0, g, CM);
     }
-    st[OC_STAT_EPISODES] = eps;
-    st[OC_STAT_SUCCESSES] = succ;
-    st[OC_STAT_STEPS] = steps;
-    st[OC_STAT_COLLISIONS] = ncoll;
-    st[OC_STAT_ERRORS] = err;
+    tally.store(st);
 }
 
 // oc_cpu_step on a wide level: words [g0, g1) (4 envs each) through the host pass of the
@@ -1981,63 +1991,46 @@ static void cpu_step_wide(const oc_handle* h, const uint8_t* sin, uint8_t* sout,
         }
         return r;
     };
-    auto rd = [P](const uint8_t* base, int plane, int64_t g) {
-        uint32_t v;
-        memcpy(&v, base + plane * P + 4 * g, 4);
-        return v;
-    };
-    auto wr = [P](uint8_t* base, int plane, int64_t g, uint32_t v) { memcpy(base + plane * P + 4 * g, &v, 4); };
-    uint64_t eps = 0, succ = 0, steps = 0, ncoll = 0, err = 0;
+    HostTally tally;
     for (int64_t g = g0; g < g1; ++g) {
         uint32_t X[A], Y[A], Hh[A], LL[K], LH[K], M[K], AC[A], EX[A], T0, T1, F, CM;
         for (int a = 0; a < A; ++a) {
-            X[a] = rd(sin, PL::X + a, g);
-            Y[a] = rd(sin, PL::Y + a, g);
-            Hh[a] = rd(sin, PL::H + a, g);
-            AC[a] = rd(act, a, g);
+            X[a] = rd(sin, P, PL::X + a, g);
+            Y[a] = rd(sin, P, PL::Y + a, g);
+            Hh[a] = rd(sin, P, PL::HOLD + a, g);
+            AC[a] = rd(act, P, a, g);
         }
         for (int j = 0; j < K; ++j) {
-            LL[j] = rd(sin, PL::L + j, g);
-            LH[j] = rd(sin, PL::LH + j, g);
-            M[j] = rd(sin, PL::M + j, g);
+            LL[j] = rd(sin, P, PL::LOC + j, g);
+            LH[j] = rd(sin, P, PL::LOC_HI + j, g);
+            M[j] = rd(sin, P, PL::MASK + j, g);
         }
         memcpy(&T0, sin + PL::T * P + 8 * g, 4);
         memcpy(&T1, sin + PL::T * P + 8 * g + 4, 4);
-        F = rd(sin, PL::F, g);
+        F = rd(sin, P, PL::F, g);
         const uint32_t f_in = F;
         uint32_t pending = ocsw::at_done80w<K>(SL, LL, LH);
         const bool full = ocsw::step4w<A, K>(SL, X, Y, Hh, LL, LH, M, T0, T1, F, AC, EX, CM, cls_of,
                                              [](uint32_t v) { return v != 0u; }, pending);
         const int64_t rem = B - g * kEPL;
-        const uint32_t vmask = rem >= kEPL ? 0xFFFFFFFFu : (1u << (8 * (uint32_t)rem)) - 1u;
-        ncoll += (uint64_t)__builtin_popcount(CM & vmask);
-        if (full) {
-            const uint32_t ended = (F & ~f_in & vmask) & ocsw::k01;
-            for (int q = 0; q < kEPL; ++q) {
-                if (!((ended >> (8 * q)) & 1u)) continue;
-                ++eps;
-                succ += (F >> (8 * q + 1)) & 1u;
-                err += (F >> (8 * q + 2)) & 1u;
-                steps += ((q < 2 ? T0 : T1) >> (16 * (q & 1))) & 0xFFFFu;
-            }
-        }
+        tally.add(rem, full, f_in, F, T0, T1, CM);
         // the batch's last word: only its columns below B are written (a host caller's buffer
         // may be exactly B bytes per plane past the pitch's start)
         const int ncol = rem >= kEPL ? kEPL : (int)rem;
         auto put = [&](uint8_t* base, int plane, uint32_t v) {
-            if (ncol == kEPL) wr(base, plane, g, v);
+            if (ncol == kEPL) wr(base, P, plane, g, v);
             else memcpy(base + plane * P + 4 * g, &v, (size_t)ncol);
         };
         for (int a = 0; a < A; ++a) {
             put(sout, PL::X + a, X[a]);
             put(sout, PL::Y + a, Y[a]);
-            put(sout, PL::H + a, Hh[a]);
+            put(sout, PL::HOLD + a, Hh[a]);
             if (exo != nullptr) put(exo, a, EX[a]);
         }
         for (int j = 0; j < K; ++j) {
-            put(sout, PL::L + j, LL[j]);
-            put(sout, PL::LH + j, LH[j]);
-            put(sout, PL::M + j, M[j]);
+            put(sout, PL::LOC + j, LL[j]);
+            put(sout, PL::LOC_HI + j, LH[j]);
+            put(sout, PL::MASK + j, M[j]);
         }
         uint8_t tb[8];
         memcpy(tb, &T0, 4);
@@ -2046,11 +2039,347 @@ static void cpu_step_wide(const oc_handle* h, const uint8_t* sin, uint8_t* sout,
         put(sout, PL::F, F);
         if (coll != nullptr) put(coll, 0, CM);
     }
-    st[OC_STAT_EPISODES] = eps;
-    st[OC_STAT_SUCCESSES] = succ;
-    st[OC_STAT_STEPS] = steps;
-    st[OC_STAT_COLLISIONS] = ncoll;
-    st[OC_STAT_ERRORS] = err;
+    tally.store(st);
+}
+
+// Kernel and worker templates are picked by generic lambdas that take their template arguments as
+// tag values.  A lambda returns OC_OK or the failing code, and the dispatcher returns that.
+template <int V>
+using IntC = std::integral_constant<int, V>;
+template <bool V>
+using BoolC = std::bool_constant<V>;
+
+// f(IntC<A>, IntC<K>): the supported (agents, item slots) shapes, listed here and nowhere else.
+template <class F>
+static int dispatch_ak(int A, int K, F&& f) {
+    switch (A * 100 + K) {
+        case 104: return f(IntC<1>{}, IntC<4>{});
+        case 204: return f(IntC<2>{}, IntC<4>{});
+        case 304: return f(IntC<3>{}, IntC<4>{});
+        case 404: return f(IntC<4>{}, IntC<4>{});
+        case 108: return f(IntC<1>{}, IntC<8>{});
+        case 208: return f(IntC<2>{}, IntC<8>{});
+        case 308: return f(IntC<3>{}, IntC<8>{});
+        case 408: return f(IntC<4>{}, IntC<8>{});
+        case 116: return f(IntC<1>{}, IntC<16>{});
+        case 216: return f(IntC<2>{}, IntC<16>{});
+        case 316: return f(IntC<3>{}, IntC<16>{});
+        case 416: return f(IntC<4>{}, IntC<16>{});
+        default: return fail(OC_EINVAL, "unsupported (A,K)=(%d,%d)", A, K);
+    }
+}
+
+// f(A, K, BoolC<wide>): narrow (byte cell ids) or wide (u16) states -- render, observe, progress,
+// checksum.
+template <class F>
+static int dispatch_w(const oc_handle* h, F&& f) {
+    return dispatch_ak(h->A, h->K, [&](auto a, auto k) {
+        return h->wide ? f(a, k, BoolC<true>{}) : f(a, k, BoolC<false>{});
+    });
+}
+
+// f(A, K, IntC<MODE>), the narrow step: 4-slot levels of the common class (H <= 8, W*H <= 128,
+// presence masks: every shipped kitchen) take the MODE 0 build of the SWAR step, everything else
+// MODE 1.
+template <class F>
+static int dispatch_step(const oc_handle* h, F&& f) {
+    const ocsw::SwarLevel& sw = h->args.sw;
+    const bool common = !sw.tall && !sw.big && !sw.counts && !sw.edge;
+    return dispatch_ak(h->A, h->K, [&](auto a, auto k) {
+        if constexpr (decltype(k)::value == 4) {
+            if (common) return f(a, k, IntC<0>{});
+        }
+        return f(a, k, IntC<1>{});
+    });
+}
+
+// f(A, K, BoolC<W>, BoolC<GD>), the planner kernels: narrow (byte cell ids) or wide (u16) rows;
+// the distance table in LDS (GD false) or in device memory (GD: every wide level, and a narrow
+// level whose graph has more than ocro::kMaxNodes nodes).
+template <class F>
+static int dispatch_plan(const oc_handle* h, F&& f) {
+    return dispatch_ak(h->A, h->K, [&](auto a, auto k) {
+        if (h->wide) return f(a, k, BoolC<true>{}, BoolC<true>{});
+        if (h->roll.dist_global) return f(a, k, BoolC<false>{}, BoolC<true>{});
+        return f(a, k, BoolC<false>{}, BoolC<false>{});
+    });
+}
+
+// Threads of a host entry point: nthreads (0: the machine's), at most one per min_units of the
+// call's units, at least one.
+static int64_t host_threads(int32_t nthreads, int64_t units, int64_t min_units) {
+    if (nthreads == 0) nthreads = (int32_t)std::thread::hardware_concurrency();
+    const int64_t most = (units + min_units - 1) / min_units;
+    const int64_t nt = nthreads < most ? nthreads : most;
+    return nt < 1 ? 1 : nt;
+}
+
+// fn(i) for the ranges i in [0, nt): ranges 1..nt-1 start on workers and range 0 runs on the
+// calling thread while they work; ranges whose thread cannot be started run here too.  The first
+// failing range's code and message come back through fail().
+template <class Fn>
+static int run_ranges(int64_t nt, Fn&& fn) {
+    std::vector<int> rcs((size_t)nt, OC_OK);
+    std::vector<std::string> msgs((size_t)nt);
+    auto run = [&](int64_t i) {
+        rcs[(size_t)i] = fn(i);
+        if (rcs[(size_t)i] != OC_OK) msgs[(size_t)i] = g_last_error;  // thread-local: the range's own
+    };
+    std::vector<std::thread> pool;
+    int64_t started = 1;
+    try {
+        for (; started < nt; ++started) pool.emplace_back(run, started);
+    } catch (const std::exception&) {  // no more threads: the rest of the ranges run here
+    }
+    run(0);
+    for (int64_t i = started; i < nt; ++i) run(i);
+    for (auto& t : pool) t.join();
+    for (int64_t i = 0; i < nt; ++i)
+        if (rcs[(size_t)i] != OC_OK) return fail(rcs[(size_t)i], "%s", msgs[(size_t)i].c_str());
+    return OC_OK;
+}
+
+// One launch of an n-step call: steps [r0, r0 + m) of it.
+struct StepLaunch {
+    const uint8_t* src;  // the state it starts from
+    uint8_t* so;         // where its final state goes; null: its last trajectory slot already holds it
+    const uint8_t* ac;   // its steps' actions
+    uint8_t *tr, *ex, *cm;  // its steps' trajectory slots, executed actions and collision masks (or null)
+    int m;
+    bool last;
+};
+
+// Splits an n-step call over states of NP planes into equal launches of at most 4,096 steps whose
+// buffer offsets (trajectory, actions) stay < 2 GiB, and calls launch(StepLaunch) for each.  With
+// a trajectory, a launch's final state is its last trajectory slot: the next launch starts from
+// there, and sout is written by the last launch only (and not at all when it is the trajectory's
+// last state).  So no launch reads a buffer it also writes.
+template <class Launch>
+static int split_steps(int64_t NP, int64_t P, int A, const void* sin, void* sout, const uint8_t* act, void* traj,
+                       uint8_t* ex, uint8_t* coll, int32_t n, Launch&& launch) {
+    if (NP * P >= (1ll << 31)) return fail(OC_EINVAL, "batch too large for one launch (state must be < 2 GiB)");
+    int64_t per = ((1ll << 31) - 1) / (NP * P);
+    if (per > 4096) per = 4096;
+    per = (n + (n + per - 1) / per - 1) / ((n + per - 1) / per);  // equal launches
+    const uint8_t* last_slot = traj ? (const uint8_t*)traj + (int64_t)(n - 1) * NP * P : nullptr;
+    const bool out_is_last = traj != nullptr && (const uint8_t*)sout == last_slot;
+    const uint8_t* src = (const uint8_t*)sin;
+    for (int64_t r0 = 0; r0 < n; r0 += per) {
+        StepLaunch s;
+        s.m = (int)(n - r0 < per ? n - r0 : per);
+        s.last = r0 + s.m >= n;
+        s.src = src;
+        s.so = (traj != nullptr && !s.last) || (out_is_last && s.last) ? nullptr : (uint8_t*)sout;
+        s.ac = act + r0 * A * P;
+        s.tr = traj ? (uint8_t*)traj + r0 * NP * P : nullptr;
+        s.ex = ex ? ex + r0 * A * P : nullptr;
+        s.cm = coll ? coll + r0 * P : nullptr;
+        if (const int rc = launch(s)) return rc;
+        src = traj != nullptr ? s.tr + (int64_t)(s.m - 1) * NP * P : (const uint8_t*)sout;
+    }
+    return OC_OK;
+}
+
+// The level's side of a wide kernel's arguments (tile_words 0: a kernel that reads no tiles).
+static WideArgs wide_args(const oc_handle* h, int64_t B, int32_t tile_words) {
+    WideArgs R;
+    R.L = h->step_lv;
+    R.S = h->step;
+    R.sw = h->args.sw;
+    R.tile_words = tile_words;
+    R.pitch = pitch_for(B);
+    R.B = B;
+    return R;
+}
+
+// A level table's device copy, or nullptr (and no HIP error left behind) when there is no device
+// to put it on, e.g. a CPU-only build check: the entry points that need the table then refuse.
+static uint8_t* upload(int device, const void* src, size_t bytes) {
+    uint8_t* d = nullptr;
+    if (hipSetDevice(device) == hipSuccess && hipMalloc(&d, bytes) == hipSuccess &&
+        hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) == hipSuccess)
+        return d;
+    (void)hipGetLastError();
+    return nullptr;
+}
+
+// the node table and the distances, as u8 (oc_reachability) or u16 (oc_reachability16)
+static int reachability(const oc_handle* h, int32_t* num_nodes, uint16_t* node_of, int64_t node_of_len, void* dist,
+                        int64_t dist_len, int out_bytes) {
+    if (h == nullptr || num_nodes == nullptr) return fail(OC_EINVAL, "bad argument");
+    ErrScope es_(h);
+    if (h->roll.nnodes < 0)
+        return fail(OC_ELEVEL, "reachability graph exceeds %d nodes (a level of more than %d cells)", ocro::kMaxNodesWide,
+                    ocro::kMaxCellsWide);
+    const int n = h->roll.nnodes, cells = h->level.width * h->level.height;
+    *num_nodes = n;
+    if (node_of != nullptr) {
+        if (node_of_len < (int64_t)cells * 5) return fail(OC_EINVAL, "node_of needs %d entries", cells * 5);
+        memcpy(node_of, h->roll_blob_host.data() + h->roll.node_off, (size_t)cells * 5 * sizeof(uint16_t));
+    }
+    if (dist != nullptr) {
+        if (dist_len < (int64_t)n * n) return fail(OC_EINVAL, "dist needs %d entries", n * n);
+        const uint8_t* src = h->roll_blob_host.data() + h->roll.dist_off;
+        const size_t nn = (size_t)n * n;
+        if (out_bytes == 1) {
+            if (h->roll.dist16)
+                return fail(OC_ELEVEL, "a BFS distance of 255 or more: the u8 table cannot hold it (oc_reachability16)");
+            memcpy(dist, src, nn);
+        } else if (h->roll.dist16) {
+            memcpy(dist, src, nn * 2);
+        } else {
+            for (size_t i = 0; i < nn; ++i) ((uint16_t*)dist)[i] = src[i] == ocro::kNone ? (uint16_t)0xFFFF : src[i];
+        }
+    }
+    return OC_OK;
+}
+
+// Wide levels: n steps of the scalar kernel (oc_step: n = 1), statistics folded by
+// oc_stats_reduce when totals are asked for.
+static int step_wide(const oc_handle* h, const void* sin, void* sout, const uint8_t* act, void* traj, uint8_t* ex,
+                     uint8_t* coll, uint64_t* stats, uint64_t* totals, int64_t B, int32_t n, void* stream) {
+    if (h->wide_tiles == nullptr) return fail(OC_EHIP, "level tables not on the device");
+    const WideArgs R = wide_args(h, B, (h->level.width * h->level.height + 3) / 4);
+    // one lane per 4 envs; up to 8 blocks per CU (grid-stride past that)
+    const int64_t need = ((B + kEPL - 1) / kEPL + kBlock - 1) / kBlock, cap = (int64_t)h->cus * 8;
+    const dim3 grid((unsigned)(need < cap ? need : cap));
+    const uint32_t rows = (uint32_t)stats_rows(h, B);
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = split_steps(ocly::num_planes(h->A, h->K, true), R.pitch, h->A, sin, sout, act, traj, ex, coll, n,
+                               [&](const StepLaunch& s) {
+        return dispatch_ak(h->A, h->K, [&](auto a, auto k) {
+            hipLaunchKernelGGL((oc_step_wide_kernel<a(), k()>), grid, dim3(kBlock), 0, st, R, h->wide_tiles, s.src,
+                               s.so, s.ac, s.tr, s.ex, s.cm, stats, rows, s.m);
+            return hip_check("oc_step (wide) launch");
+        });
+    });
+    if (rc != OC_OK) return rc;
+    return totals != nullptr ? oc_stats_reduce(h, stats, B, totals, stream) : OC_OK;
+}
+
+// Shared argument block of oc_rollout / oc_nav_likelihood / oc_subtask_bounds: level tables +
+// validated subtasks.  rollout: oc_rollout's call (Level-1 configurations allowed; the
+// node-to-square table staged only for launches of one round of blocks, below).
+static int roll_args(const oc_handle* h, const oc_subtask* subtasks, int32_t num_subtasks, int64_t B, RollArgs& R,
+                     bool rollout = false) {
+    for (int i = 0; i < num_subtasks && subtasks != nullptr; ++i)
+        if (subtasks[i].level != OC_LEVEL0 && !rollout)
+            return fail(OC_EINVAL, "subtask %d: only oc_rollout takes OC_LEVEL1", i);
+    if (num_subtasks < 1 || num_subtasks > OC_MAX_SUBTASKS) return fail(OC_EINVAL, "num_subtasks %d", num_subtasks);
+    if (h->roll.nnodes < 0)
+        return fail(OC_ELEVEL, "reachability graph exceeds %d nodes (a level of more than %d cells)", ocro::kMaxNodesWide,
+                    ocro::kMaxCellsWide);
+    if (h->roll_blob == nullptr) return fail(OC_EHIP, "rollout tables not on the device");
+    R.L = h->roll;
+    R.nsub = num_subtasks;
+    R.blob_words = h->roll.lds_bytes / 4;  // staged in LDS: the whole blob, or the tables before the distances
+    if (R.L.sq_off != 0 && rollout && B > (int64_t)h->cus * kRollBlock) {
+        // The node-to-square table (the blob's tail) shortens the one-agent Merge bound from ~3.8
+        // to 1.1-2.0 us of a wave.  A rollout launch of one round of blocks (the planner's latency
+        // shape) gains (9.03 -> 8.87 us at 4096 rows); past that every rollout block stages 40%
+        // more table for one row per lane (11.16-11.34 -> 11.35-11.51 us at 2^18: tools/rollx.hip,
+        // profiles/r06/pass_i), so larger rollouts search B's approach nodes as before.  The bounds
+        // kernel (many configurations per staged table) gains at every size, 96-97 -> 85 us at C5,
+        // and the likelihood kernels are unchanged (profiles/r06/pass_w).
+        R.blob_words = R.L.sq_off / 4;
+        R.L.sq_off = 0;
+    }
+    R.pitch = pitch_for(B);
+    R.B = B;
+    for (int i = 0; i < num_subtasks; ++i) {
+        const oc_subtask& s = subtasks[i];
+        if (s.kind < OC_SUB_NONE || s.kind > OC_SUB_DELIVER) return fail(OC_EINVAL, "subtask %d kind %d", i, s.kind);
+        if (s.num_agents < 1 || s.num_agents > 2) return fail(OC_EINVAL, "subtask %d: %d agents", i, s.num_agents);
+        for (int q = 0; q < s.num_agents; ++q)
+            if (s.agent[q] >= h->A) return fail(OC_EINVAL, "subtask %d: agent %d", i, s.agent[q]);
+        if (s.num_agents == 2 && s.agent[0] >= s.agent[1]) return fail(OC_EINVAL, "subtask %d: agents not ascending", i);
+        ocro::Sub& d = R.subs[i];
+        d.kind = s.kind;
+        d.n = s.num_agents;
+        d.agent[0] = s.agent[0];
+        d.agent[1] = s.num_agents == 2 ? s.agent[1] : s.agent[0];
+        d.start[0] = s.start_mask[0];
+        d.start[1] = s.start_mask[1];
+        if (s.level > OC_LEVEL1) return fail(OC_EINVAL, "subtask %d: level %d", i, s.level);
+        d.goal = s.goal_mask;
+        d.count = s.goal_count;
+        d.level = s.level;
+        d.pad = 0;
+    }
+    return OC_OK;
+}
+
+// The planner kernels stage the level's table blob in dynamic LDS.  Past the 64 KB a launch gets
+// by default (graphs of more than ~245 nodes) the kernel must be allowed more, up to the CU's
+// 160 KB; the kernel's static LDS counts against the same limit.
+constexpr int kLdsPerCu = 160 * 1024;
+static int allow_dyn_lds(const void* kernel, int dyn) {
+    if (dyn <= 48 * 1024) return OC_OK;
+    hipFuncAttributes fa;
+    if (hipFuncGetAttributes(&fa, kernel) != hipSuccess) return hip_check("hipFuncGetAttributes");
+    if ((int64_t)fa.sharedSizeBytes + dyn > kLdsPerCu)
+        return fail(OC_ELEVEL, "level tables (%d B) and the kernel's LDS (%d B) exceed %d B", dyn,
+                    (int)fa.sharedSizeBytes, kLdsPerCu);
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, dyn) != hipSuccess)
+        return hip_check("hipFuncSetAttribute");
+    return OC_OK;
+}
+
+// oc_observe / oc_cpu_observe: the arguments both check, and the level's side of ObsArgs
+static int observe_args(const oc_handle* h, const void* state, const void* obs, const uint8_t* action_mask,
+                        int32_t dtype, int32_t view_agent, int64_t B, ocob::ObsArgs& R) {
+    if (state == nullptr || B < 0) return fail(OC_EINVAL, "bad argument");
+    if (obs == nullptr && action_mask == nullptr) return fail(OC_EINVAL, "observe: obs and action_mask are both NULL");
+    if (dtype != OC_OBS_U8 && dtype != OC_OBS_F16) return fail(OC_EINVAL, "observe: dtype %d (OC_OBS_U8 or OC_OBS_F16)", dtype);
+    if (view_agent < -1 || view_agent >= h->A)
+        return fail(OC_EINVAL, "observe: view_agent %d outside [-1, %d)", view_agent, h->A);
+    if (((uintptr_t)state & 15u) || ((uintptr_t)action_mask & 3u) || (dtype == OC_OBS_F16 && ((uintptr_t)obs & 1u)))
+        return fail(OC_EINVAL, "misaligned buffer");
+    R = ocob::ObsArgs{};
+    R.W = h->level.width;
+    R.H = h->level.height;
+    R.HW = R.W * R.H;
+    R.C = OC_OBS_CHANNELS(h->A);
+    R.CHW = R.C * R.HW;
+    R.counts = h->level.encoding == OC_ENC_COUNTS;
+    R.rot = view_agent < 0 ? 0 : view_agent;
+    R.nstatic = h->obs_nstatic;
+    R.nt = h->obs_nt;
+    R.pitch = pitch_for(B);
+    R.B = B;
+    return OC_OK;
+}
+
+// oc_progress / oc_cpu_progress: the arguments both check, and the call's ProgArgs
+static int progress_args(const oc_handle* h, const void* state_prev, const void* states, int32_t n,
+                         const oc_subtask* subtasks, int32_t num_subtasks, const float* weights, const uint8_t* counts,
+                         const uint8_t* events, const float* reward, int64_t B, ocpg::ProgArgs& R) {
+    if (state_prev == nullptr || states == nullptr || subtasks == nullptr || B < 0) return fail(OC_EINVAL, "bad argument");
+    if (n < 1) return fail(OC_EINVAL, "progress: n = %d (at least 1)", n);
+    if (num_subtasks < 1 || num_subtasks > OC_MAX_SUBTASKS)
+        return fail(OC_EINVAL, "progress: num_subtasks %d outside [1, %d]", num_subtasks, OC_MAX_SUBTASKS);
+    if (counts == nullptr && events == nullptr && reward == nullptr)
+        return fail(OC_EINVAL, "progress: counts, events and reward are all NULL");
+    if (((uintptr_t)state_prev & 3u) || ((uintptr_t)states & 3u) || ((uintptr_t)counts & 3u) ||
+        ((uintptr_t)events & 3u) || ((uintptr_t)reward & 15u))
+        return fail(OC_EINVAL, "misaligned buffer");
+    R = ocpg::ProgArgs{};
+    for (int i = 0; i < num_subtasks; ++i) {
+        const int32_t kind = subtasks[i].kind;
+        if (kind != OC_SUB_NONE && kind != OC_SUB_CHOP && kind != OC_SUB_MERGE && kind != OC_SUB_DELIVER)
+            return fail(OC_EINVAL, "progress: subtask %d has kind %d", i, kind);
+        R.sub[i] = (uint32_t)kind << 8 | subtasks[i].goal_mask;
+        R.weight[i] = weights != nullptr ? weights[i] : 1.0f;
+    }
+    R.W = h->level.width;
+    R.tile_words = (h->level.width * h->level.height + 3) / 4;
+    R.n = n;
+    R.S = num_subtasks;
+    R.planes = OC_PROGRESS_EVENT_PLANES(num_subtasks);
+    R.pitch = pitch_for(B);
+    R.B = B;
+    R.state_bytes = (int64_t)ocly::num_planes(h->A, h->K, h->wide) * R.pitch;
+    return OC_OK;
 }
 
 extern "C" {
@@ -2204,24 +2533,13 @@ int oc_create(const oc_level_desc* lv, int32_t num_agents, int32_t max_T, int32_
             h->roll.nnodes = -1;
         } else if (!host_only) {
             h->roll_blob_bytes = h->roll.blob_bytes;
-            if (hipSetDevice(device) != hipSuccess ||
-                hipMalloc(&h->roll_blob, (size_t)h->roll_blob_bytes) != hipSuccess ||
-                hipMemcpy(h->roll_blob, h->roll_blob_host.data(), (size_t)h->roll_blob_bytes, hipMemcpyHostToDevice) !=
-                    hipSuccess) {
-                h->roll_blob = nullptr;  // no device (e.g. a CPU-only build check): rollout unavailable
-                (void)hipGetLastError();
-            }
+            // null: rollout unavailable
+            h->roll_blob = upload(device, h->roll_blob_host.data(), (size_t)h->roll_blob_bytes);
         }
     }
     if (h->roll.nnodes >= 0) h->roll_blob_bytes = h->roll.blob_bytes;
-    if (wide && !host_only) {
-        const size_t tb = (size_t)((W * H + 3) & ~3);
-        if (hipSetDevice(device) != hipSuccess || hipMalloc(&h->wide_tiles, tb) != hipSuccess ||
-            hipMemcpy(h->wide_tiles, h->wide_tiles_host, tb, hipMemcpyHostToDevice) != hipSuccess) {
-            h->wide_tiles = nullptr;  // no device: oc_cpu_step only
-            (void)hipGetLastError();
-        }
-    }
+    // null: oc_cpu_step only
+    if (wide && !host_only) h->wide_tiles = upload(device, h->wide_tiles_host, (size_t)((W * H + 3) & ~3));
     {  // oc_observe's level table
         const int cells = W * H, off = (cells + 3) & ~3;
         std::vector<uint16_t> st;
@@ -2237,47 +2555,10 @@ int oc_create(const oc_level_desc* lv, int32_t num_agents, int32_t max_T, int32_
             const int v = atoi(e);
             if (v >= 1 && v <= ocob::kMaxTileEnvs && (v & (v - 1)) == 0) h->obs_tile = v;
         }
-        if (!host_only) {
-            if (hipSetDevice(device) != hipSuccess || hipMalloc(&h->obs_tab, h->obs_tab_host.size()) != hipSuccess ||
-                hipMemcpy(h->obs_tab, h->obs_tab_host.data(), h->obs_tab_host.size(), hipMemcpyHostToDevice) !=
-                    hipSuccess) {
-                h->obs_tab = nullptr;  // no device: oc_cpu_observe only
-                (void)hipGetLastError();
-            }
-        }
+        // null: oc_cpu_observe only
+        if (!host_only) h->obs_tab = upload(device, h->obs_tab_host.data(), h->obs_tab_host.size());
     }
     *out = h;
-    return OC_OK;
-}
-
-// the node table and the distances, as u8 (oc_reachability) or u16 (oc_reachability16)
-static int reachability(const oc_handle* h, int32_t* num_nodes, uint16_t* node_of, int64_t node_of_len, void* dist,
-                        int64_t dist_len, int out_bytes) {
-    if (h == nullptr || num_nodes == nullptr) return fail(OC_EINVAL, "bad argument");
-    ErrScope es_(h);
-    if (h->roll.nnodes < 0)
-        return fail(OC_ELEVEL, "reachability graph exceeds %d nodes (a level of more than %d cells)", ocro::kMaxNodesWide,
-                    ocro::kMaxCellsWide);
-    const int n = h->roll.nnodes, cells = h->level.width * h->level.height;
-    *num_nodes = n;
-    if (node_of != nullptr) {
-        if (node_of_len < (int64_t)cells * 5) return fail(OC_EINVAL, "node_of needs %d entries", cells * 5);
-        memcpy(node_of, h->roll_blob_host.data() + h->roll.node_off, (size_t)cells * 5 * sizeof(uint16_t));
-    }
-    if (dist != nullptr) {
-        if (dist_len < (int64_t)n * n) return fail(OC_EINVAL, "dist needs %d entries", n * n);
-        const uint8_t* src = h->roll_blob_host.data() + h->roll.dist_off;
-        const size_t nn = (size_t)n * n;
-        if (out_bytes == 1) {
-            if (h->roll.dist16)
-                return fail(OC_ELEVEL, "a BFS distance of 255 or more: the u8 table cannot hold it (oc_reachability16)");
-            memcpy(dist, src, nn);
-        } else if (h->roll.dist16) {
-            memcpy(dist, src, nn * 2);
-        } else {
-            for (size_t i = 0; i < nn; ++i) ((uint16_t*)dist)[i] = src[i] == ocro::kNone ? (uint16_t)0xFFFF : src[i];
-        }
-    }
     return OC_OK;
 }
 
@@ -2302,163 +2583,22 @@ int oc_destroy(oc_handle* h) {
 int oc_get_layout(const oc_handle* h, int64_t B, oc_layout* out) {
     if (h == nullptr || out == nullptr || B < 0) return fail(OC_EINVAL, "bad argument");
     ErrScope es_(h);
-    const int A = h->A, K = h->K;
+    const ocly::Layout l = ocly::layout(h->A, h->K, h->wide);
     out->pitch = pitch_for(B);
-    out->num_agents = A;
-    out->num_items = K;
-    out->plane_agent_x = 0;
-    out->plane_agent_y = A;
-    out->plane_agent_hold = 2 * A;
-    const int LK = h->wide ? 2 * K : K;  // item cell planes: low bytes, then (wide) high bytes
-    out->plane_item_loc = 3 * A;
-    out->plane_item_loc_hi = h->wide ? 3 * A + K : -1;
+    out->num_agents = h->A;
+    out->num_items = h->K;
+    out->plane_agent_x = l.X;
+    out->plane_agent_y = l.Y;
+    out->plane_agent_hold = l.HOLD;
+    out->plane_item_loc = l.LOC;
+    out->plane_item_loc_hi = l.LOC_HI;
     out->cell_bytes = h->wide ? 2 : 1;
-    out->plane_item_mask = 3 * A + LK;
-    out->plane_t = 3 * A + LK + K;
-    out->plane_flags = 3 * A + LK + K + 2;
-    out->num_planes = 3 * A + LK + K + 3;
+    out->plane_item_mask = l.MASK;
+    out->plane_t = l.T;
+    out->plane_flags = l.F;
+    out->num_planes = l.NP;
     out->state_bytes = out->num_planes * out->pitch;
     return OC_OK;
-}
-
-#define OC_DISPATCH(A_, K_, LAUNCH)                                                         \
-    switch ((A_) * ((K_) >= 10 ? 100 : 10) + (K_)) {                                        \
-        case 14: LAUNCH(1, 4); break;                                                       \
-        case 24: LAUNCH(2, 4); break;                                                       \
-        case 34: LAUNCH(3, 4); break;                                                       \
-        case 44: LAUNCH(4, 4); break;                                                       \
-        case 18: LAUNCH(1, 8); break;                                                       \
-        case 28: LAUNCH(2, 8); break;                                                       \
-        case 38: LAUNCH(3, 8); break;                                                       \
-        case 48: LAUNCH(4, 8); break;                                                       \
-        case 116: LAUNCH(1, 16); break;                                                     \
-        case 216: LAUNCH(2, 16); break;                                                     \
-        case 316: LAUNCH(3, 16); break;                                                     \
-        case 416: LAUNCH(4, 16); break;                                                     \
-        default: return fail(OC_EINVAL, "unsupported (A,K)=(%d,%d)", (A_), (K_));           \
-    }
-
-// The planner kernels: LAUNCH(A, K, W, GD): narrow (byte cell ids) or wide (u16) rows; the
-// distance table in LDS (GD false) or in device memory (GD: every wide level, and a narrow level
-// whose graph has more than ocro::kMaxNodes nodes).
-#define OC_DISPATCH_PLAN(h_, LAUNCH)                                                        \
-    if ((h_)->wide) {                                                                       \
-        OC_DISPATCH((h_)->A, (h_)->K, OC_PLAN_WIDE)                                         \
-    } else if ((h_)->roll.dist_global) {                                                    \
-        OC_DISPATCH((h_)->A, (h_)->K, OC_PLAN_NARROW_GD)                                    \
-    } else {                                                                                \
-        OC_DISPATCH((h_)->A, (h_)->K, OC_PLAN_NARROW)                                       \
-    }
-
-// The render kernel: narrow (byte cell ids) or wide (u16) rows.
-#define OC_DISPATCH_W(h_, LAUNCH)                                                           \
-    if ((h_)->wide) {                                                                       \
-        switch ((h_)->A * ((h_)->K >= 10 ? 100 : 10) + (h_)->K) {                           \
-            case 14: LAUNCH(1, 4, true); break;                                             \
-            case 24: LAUNCH(2, 4, true); break;                                             \
-            case 34: LAUNCH(3, 4, true); break;                                             \
-            case 44: LAUNCH(4, 4, true); break;                                             \
-            case 18: LAUNCH(1, 8, true); break;                                             \
-            case 28: LAUNCH(2, 8, true); break;                                             \
-            case 38: LAUNCH(3, 8, true); break;                                             \
-            case 48: LAUNCH(4, 8, true); break;                                             \
-            case 116: LAUNCH(1, 16, true); break;                                           \
-            case 216: LAUNCH(2, 16, true); break;                                           \
-            case 316: LAUNCH(3, 16, true); break;                                           \
-            case 416: LAUNCH(4, 16, true); break;                                           \
-            default: return fail(OC_EINVAL, "unsupported (A,K)=(%d,%d)", (h_)->A, (h_)->K); \
-        }                                                                                   \
-    } else {                                                                                \
-        switch ((h_)->A * ((h_)->K >= 10 ? 100 : 10) + (h_)->K) {                           \
-            case 14: LAUNCH(1, 4, false); break;                                            \
-            case 24: LAUNCH(2, 4, false); break;                                            \
-            case 34: LAUNCH(3, 4, false); break;                                            \
-            case 44: LAUNCH(4, 4, false); break;                                            \
-            case 18: LAUNCH(1, 8, false); break;                                            \
-            case 28: LAUNCH(2, 8, false); break;                                            \
-            case 38: LAUNCH(3, 8, false); break;                                            \
-            case 48: LAUNCH(4, 8, false); break;                                            \
-            case 116: LAUNCH(1, 16, false); break;                                          \
-            case 216: LAUNCH(2, 16, false); break;                                          \
-            case 316: LAUNCH(3, 16, false); break;                                          \
-            case 416: LAUNCH(4, 16, false); break;                                          \
-            default: return fail(OC_EINVAL, "unsupported (A,K)=(%d,%d)", (h_)->A, (h_)->K); \
-        }                                                                                   \
-    }
-
-// The step kernels: 4-slot levels of the common class (H <= 8, W*H <= 128, presence masks:
-// every shipped kitchen) take the MODE 0 build of the SWAR step, everything else MODE 1.
-#define OC_DISPATCH_STEP(h_, LAUNCH)                                                        \
-    if ((h_)->K == 4 && !(h_)->args.sw.tall && !(h_)->args.sw.big && !(h_)->args.sw.counts &&  \
-        !(h_)->args.sw.edge) {                                                              \
-        switch ((h_)->A) {                                                                  \
-            case 1: LAUNCH(1, 4, 0); break;                                                 \
-            case 2: LAUNCH(2, 4, 0); break;                                                 \
-            case 3: LAUNCH(3, 4, 0); break;                                                 \
-            case 4: LAUNCH(4, 4, 0); break;                                                 \
-            default: return fail(OC_EINVAL, "unsupported A=%d", (h_)->A);                   \
-        }                                                                                   \
-    } else {                                                                                \
-        switch ((h_)->A * ((h_)->K >= 10 ? 100 : 10) + (h_)->K) {                           \
-            case 14: LAUNCH(1, 4, 1); break;                                                \
-            case 24: LAUNCH(2, 4, 1); break;                                                \
-            case 34: LAUNCH(3, 4, 1); break;                                                \
-            case 44: LAUNCH(4, 4, 1); break;                                                \
-            case 18: LAUNCH(1, 8, 1); break;                                                \
-            case 28: LAUNCH(2, 8, 1); break;                                                \
-            case 38: LAUNCH(3, 8, 1); break;                                                \
-            case 48: LAUNCH(4, 8, 1); break;                                                \
-            case 116: LAUNCH(1, 16, 1); break;                                              \
-            case 216: LAUNCH(2, 16, 1); break;                                              \
-            case 316: LAUNCH(3, 16, 1); break;                                              \
-            case 416: LAUNCH(4, 16, 1); break;                                              \
-            default: return fail(OC_EINVAL, "unsupported (A,K)=(%d,%d)", (h_)->A, (h_)->K); \
-        }                                                                                   \
-    }
-
-// Wide levels: n steps of the scalar kernel (oc_step: n = 1), statistics folded by
-// oc_stats_reduce when totals are asked for.
-static int step_wide(const oc_handle* h, const void* sin, void* sout, const uint8_t* act, void* traj, uint8_t* ex,
-                     uint8_t* coll, uint64_t* stats, uint64_t* totals, int64_t B, int32_t n, void* stream) {
-    if (h->wide_tiles == nullptr) return fail(OC_EHIP, "level tables not on the device");
-    WideArgs R;
-    R.L = h->step_lv;
-    R.S = h->step;
-    R.sw = h->args.sw;
-    R.tile_words = (h->level.width * h->level.height + 3) / 4;
-    R.pitch = pitch_for(B);
-    R.B = B;
-    // one lane per 4 envs; up to 8 blocks per CU (grid-stride past that)
-    const int64_t need = ((B + kEPL - 1) / kEPL + kBlock - 1) / kBlock, cap = (int64_t)h->cus * 8;
-    const dim3 grid((unsigned)(need < cap ? need : cap));
-    const uint32_t rows = (uint32_t)stats_rows(h, B);
-    hipStream_t st = (hipStream_t)stream;
-    // launches of at most `per` steps, so a launch's buffer offsets (trajectory, actions) stay
-    // < 2 GiB; each starts from the previous one's final state (as oc_step_n's narrow path)
-    const int64_t NP = 3 * h->A + 3 * h->K + 3, P = R.pitch;
-    if (NP * P >= (1ll << 31)) return fail(OC_EINVAL, "batch too large for one launch (state must be < 2 GiB)");
-    int64_t per = ((1ll << 31) - 1) / (NP * P);
-    if (per > 4096) per = 4096;
-    per = (n + (n + per - 1) / per - 1) / ((n + per - 1) / per);  // equal launches
-    const uint8_t* last_slot = traj ? (const uint8_t*)traj + (int64_t)(n - 1) * NP * P : nullptr;
-    const bool out_is_last = traj != nullptr && (const uint8_t*)sout == last_slot;
-    const uint8_t* src = (const uint8_t*)sin;
-    for (int64_t r0 = 0; r0 < n; r0 += per) {
-        const int m = (int)(n - r0 < per ? n - r0 : per);
-        const bool last = r0 + m >= n;
-        uint8_t* tr = traj ? (uint8_t*)traj + r0 * NP * P : nullptr;
-        uint8_t* so = (traj != nullptr && !last) || (out_is_last && last) ? nullptr : (uint8_t*)sout;
-        uint8_t* e_ = ex ? ex + r0 * h->A * P : nullptr;
-        uint8_t* c_ = coll ? coll + r0 * P : nullptr;
-        const uint8_t* a_ = act + r0 * h->A * P;
-#define OC_LAUNCH_WSTEP(A, K)                                                                                  \
-    hipLaunchKernelGGL((oc_step_wide_kernel<A, K>), grid, dim3(kBlock), 0, st, R, h->wide_tiles, src, so, a_,  \
-                       tr, e_, c_, stats, rows, m)
-        OC_DISPATCH(h->A, h->K, OC_LAUNCH_WSTEP)
-        if (const int rc = hip_check("oc_step (wide) launch")) return rc;
-        src = traj != nullptr ? tr + (int64_t)(m - 1) * NP * P : (const uint8_t*)sout;
-    }
-    return totals != nullptr ? oc_stats_reduce(h, stats, B, totals, stream) : OC_OK;
 }
 
 int oc_reset(const oc_handle* h, void* state, int64_t B, void* stream) {
@@ -2466,28 +2606,23 @@ int oc_reset(const oc_handle* h, void* state, int64_t B, void* stream) {
     ErrScope es_(h);
     OC_NEED_DEVICE(h);
     if (B == 0) return OC_OK;
+    hipStream_t s = (hipStream_t)stream;
     if (h->wide) {
-        WideArgs R;
-        R.L = h->step_lv;
-        R.S = h->step;
-        R.sw = h->args.sw;
-        R.tile_words = 0;
-        R.pitch = pitch_for(B);
-        R.B = B;
+        const WideArgs R = wide_args(h, B, 0);
         const dim3 grid((unsigned)(R.pitch / kBlock));
-        hipStream_t st = (hipStream_t)stream;
-#define OC_LAUNCH_WRESET(A, K) hipLaunchKernelGGL((oc_reset_wide_kernel<A, K>), grid, dim3(kBlock), 0, st, R, (uint8_t*)state)
-        OC_DISPATCH(h->A, h->K, OC_LAUNCH_WRESET)
-        return hip_check("oc_reset (wide) launch");
+        return dispatch_ak(h->A, h->K, [&](auto a, auto k) {
+            hipLaunchKernelGGL((oc_reset_wide_kernel<a(), k()>), grid, dim3(kBlock), 0, s, R, (uint8_t*)state);
+            return hip_check("oc_reset (wide) launch");
+        });
     }
     LevelArgs L = h->args;
     L.pitch = pitch_for(B);
     L.B = B;
     const dim3 grid((unsigned)(L.pitch / kEnvsPerBlock));
-    hipStream_t s = (hipStream_t)stream;
-#define OC_LAUNCH_RESET(A, K) hipLaunchKernelGGL((oc_reset_kernel<A, K>), grid, dim3(kBlock), 0, s, L, (uint8_t*)state)
-    OC_DISPATCH(h->A, h->K, OC_LAUNCH_RESET)
-    return hip_check("oc_reset launch");
+    return dispatch_ak(h->A, h->K, [&](auto a, auto k) {
+        hipLaunchKernelGGL((oc_reset_kernel<a(), k()>), grid, dim3(kBlock), 0, s, L, (uint8_t*)state);
+        return hip_check("oc_reset launch");
+    });
 }
 
 int oc_step(const oc_handle* h, const void* state_in, void* state_out, const uint8_t* actions,
@@ -2504,16 +2639,16 @@ int oc_step(const oc_handle* h, const void* state_in, void* state_out, const uin
     LevelArgs L = h->args;
     L.pitch = pitch_for(B);
     L.B = B;
-    if ((int64_t)(3 * h->A + 2 * h->K + 3) * L.pitch >= (1ll << 31))
+    if ((int64_t)ocly::num_planes(h->A, h->K, false) * L.pitch >= (1ll << 31))
         return fail(OC_EINVAL, "batch too large for one launch (state must be < 2 GiB)");
     const dim3 grid((unsigned)(L.pitch / kEPL / kStepBlock));  // pitch is a multiple of 4096
     const uint32_t rows = (uint32_t)stats_rows(h, B);
     hipStream_t s = (hipStream_t)stream;
-#define OC_LAUNCH_STEP(A, K, MODE)                                                                        \
-    hipLaunchKernelGGL((oc_step_kernel<A, K, MODE>), grid, dim3(kStepBlock), 0, s, L, (const uint8_t*)state_in, \
-                       (uint8_t*)state_out, actions, exec_actions, coll_mask, stats, rows)
-    OC_DISPATCH_STEP(h, OC_LAUNCH_STEP)
-    return hip_check("oc_step launch");
+    return dispatch_step(h, [&](auto a, auto k, auto mode) {
+        hipLaunchKernelGGL((oc_step_kernel<a(), k(), mode()>), grid, dim3(kStepBlock), 0, s, L,
+                           (const uint8_t*)state_in, (uint8_t*)state_out, actions, exec_actions, coll_mask, stats, rows);
+        return hip_check("oc_step launch");
+    });
 }
 
 int oc_cpu_step(const oc_handle* h, const void* state_in, void* state_out, const uint8_t* actions,
@@ -2523,58 +2658,23 @@ int oc_cpu_step(const oc_handle* h, const void* state_in, void* state_out, const
     ErrScope es_(h);
     if (B == 0) return OC_OK;
     const int64_t P = pitch_for(B), words = (B + kEPL - 1) / kEPL;
-    if (nthreads == 0) nthreads = (int32_t)std::thread::hardware_concurrency();
-    int64_t nt = nthreads < 1 ? 1 : nthreads;
-    if (nt > (words + 4095) / 4096) nt = (words + 4095) / 4096;  // >= 4096 words (16 Ki envs) per thread
-    if (nt < 1) nt = 1;
+    const int64_t nt = host_threads(nthreads, words, 4096);  // >= 4096 words (16 Ki envs) per thread
     std::vector<uint64_t> part((size_t)nt * OC_NSTATS, 0);
-    auto run = [&](int64_t i) {
+    const int rc = run_ranges(nt, [&](int64_t i) {
         const int64_t g0 = words * i / nt, g1 = words * (i + 1) / nt;
         const uint8_t* si = (const uint8_t*)state_in;
         uint8_t* so = (uint8_t*)state_out;
         uint64_t* st = part.data() + i * OC_NSTATS;
-        if (h->wide) {  // the wide SWAR step (step4w), four envs per word as the kernel
-#define OC_CPU_WSTEP(A, K) cpu_step_wide<A, K>(h, si, so, actions, exec_actions, coll_mask, B, P, g0, g1, st)
-            OC_DISPATCH(h->A, h->K, OC_CPU_WSTEP)
-#undef OC_CPU_WSTEP
-            return OC_OK;
-        }
-#define OC_CPU_STEP(A, K, MODE) cpu_step_words<A, K, MODE>(h, si, so, actions, exec_actions, coll_mask, B, P, g0, g1, st)
-        OC_DISPATCH_STEP(h, OC_CPU_STEP)
-#undef OC_CPU_STEP
-        return OC_OK;
-    };
-    // Every range runs the same (A, K, MODE) dispatch, so it is checked once here, on the calling
-    // thread (an unsupported shape fails before any thread starts).  Then ranges 1..nt-1 start on
-    // workers and range 0 runs on the calling thread while they work; a worker's failure message
-    // is still carried back.  Ranges whose thread cannot be started run here too.
-#define OC_CPU_NOP(...) (void)0
-    if (h->wide) {
-        OC_DISPATCH(h->A, h->K, OC_CPU_NOP)
-    } else {
-        OC_DISPATCH_STEP(h, OC_CPU_NOP)
-    }
-#undef OC_CPU_NOP
-    std::vector<std::thread> pool;
-    std::vector<int> rcs((size_t)nt, OC_OK);
-    std::vector<std::string> msgs((size_t)nt);
-    int64_t started = 1;
-    try {
-        for (; started < nt; ++started)
-            pool.emplace_back([&, i = started] {
-                rcs[(size_t)i] = run(i);
-                if (rcs[(size_t)i] != OC_OK) msgs[(size_t)i] = g_last_error;
+        if (h->wide)  // the wide SWAR step (step4w), four envs per word as the kernel
+            return dispatch_ak(h->A, h->K, [&](auto a, auto k) {
+                cpu_step_wide<a(), k()>(h, si, so, actions, exec_actions, coll_mask, B, P, g0, g1, st);
+                return OC_OK;
             });
-    } catch (const std::exception&) {  // no more threads: the rest of the ranges run here
-    }
-    int rc = run(0);
-    for (int64_t i = started; i < nt; ++i) {
-        rcs[(size_t)i] = run(i);
-        if (rcs[(size_t)i] != OC_OK) msgs[(size_t)i] = g_last_error;
-    }
-    for (auto& t : pool) t.join();
-    for (int64_t i = 1; i < nt && rc == OC_OK; ++i)
-        if (rcs[(size_t)i] != OC_OK) rc = fail(rcs[(size_t)i], "%s", msgs[(size_t)i].c_str());
+        return dispatch_step(h, [&](auto a, auto k, auto mode) {
+            cpu_step_words<a(), k(), mode()>(h, si, so, actions, exec_actions, coll_mask, B, P, g0, g1, st);
+            return OC_OK;
+        });
+    });
     if (rc == OC_OK && totals != nullptr)
         for (int64_t i = 0; i < nt; ++i)
             for (int c = 0; c < OC_NSTATS; ++c) totals[c] += part[(size_t)(i * OC_NSTATS + c)];
@@ -2597,7 +2697,7 @@ int oc_step_n(const oc_handle* h, const void* state_in, void* state_out, const u
     LevelArgs L = h->args;
     L.pitch = pitch_for(B);
     L.B = B;
-    const int64_t NP = 3 * h->A + (h->wide ? 3 : 2) * h->K + 3;
+    const int64_t NP = ocly::num_planes(h->A, h->K, h->wide);
     // state_out may be the trajectory's last state (written once); nothing else may overlap it
     const uint8_t* last_slot = traj ? (const uint8_t*)traj + (int64_t)(n - 1) * NP * L.pitch : nullptr;
     const bool out_is_last = traj != nullptr && (const uint8_t*)state_out == last_slot;
@@ -2611,109 +2711,21 @@ int oc_step_n(const oc_handle* h, const void* state_in, void* state_out, const u
             return fail(OC_EINVAL, "traj must not overlap the state (state_out may be its last state)");
     }
     if (h->wide) return step_wide(h, state_in, state_out, actions, traj, exec_actions, coll_mask, stats, totals, B, n, stream);
-    if (NP * L.pitch >= (1ll << 31)) return fail(OC_EINVAL, "batch too large for one launch (state must be < 2 GiB)");
-    // steps per launch so every per-launch buffer (trajectory, actions) stays < 2 GiB of offsets
-    int64_t per = ((1ll << 31) - 1) / (NP * L.pitch);
-    if (per > 4096) per = 4096;
-    per = (n + (n + per - 1) / per - 1) / ((n + per - 1) / per);  // equal launches
     // <= 5 waves per SIMD resident: 5 blocks of 4 waves per CU, or 4 of 5 with the loader wave
     const int64_t need = L.pitch / kEnvsPerBlock;
     hipStream_t s = (hipStream_t)stream;
     const uint32_t rows = (uint32_t)stats_rows(h, B);
-    const uint8_t* src = (const uint8_t*)state_in;
-    for (int64_t r0 = 0; r0 < n; r0 += per) {
-        const int m = (int)(n - r0 < per ? n - r0 : per);
-        const int64_t off = r0;
-        uint8_t* tr = traj ? (uint8_t*)traj + off * NP * L.pitch : nullptr;
-        uint8_t* ex = exec_actions ? exec_actions + off * h->A * L.pitch : nullptr;
-        uint8_t* cm = coll_mask ? coll_mask + off * L.pitch : nullptr;
-        const uint8_t* ac = actions + off * h->A * L.pitch;
-        // With a trajectory, a launch's final state is its last trajectory slot: the next launch
-        // starts from there, and state_out is written by the last launch only (and not at all
-        // when it is the trajectory's last state).  So no launch reads a buffer it also writes.
-        const bool last = r0 + m >= n;
-        uint8_t* so = (traj != nullptr && !last) || (out_is_last && last) ? nullptr : (uint8_t*)state_out;
-#define OC_LAUNCH_STEPN(A, K, MODE)                                                                    \
-    {                                                                                                  \
-        constexpr bool kLW = use_loader_wave<A, K, MODE>();                                           \
-        const int64_t cap = (int64_t)h->cus * (kLW ? 4 : 5);                                           \
-        const dim3 grid((unsigned)(need < cap ? need : cap));                                          \
-        hipLaunchKernelGGL((oc_step_n_kernel<A, K, kCPnt, 0, MODE>), grid, dim3(kBlock + (kLW ? 64 : 0)), 0, s, L, \
-                           src, so, ac, tr, ex, cm, stats, last ? totals : nullptr, rows, m);                 \
-    }
-        OC_DISPATCH_STEP(h, OC_LAUNCH_STEPN)
-        src = traj != nullptr ? tr + (int64_t)(m - 1) * NP * L.pitch : (const uint8_t*)state_out;
-        if (const int rc = hip_check("oc_step_n launch")) return rc;
-    }
-    return OC_OK;
-}
-
-// Shared argument block of oc_rollout / oc_nav_likelihood / oc_subtask_bounds: level tables +
-// validated subtasks.  rollout: oc_rollout's call (Level-1 configurations allowed; the
-// node-to-square table staged only for launches of one round of blocks, below).
-static int roll_args(const oc_handle* h, const oc_subtask* subtasks, int32_t num_subtasks, int64_t B, RollArgs& R,
-                     bool rollout = false) {
-    for (int i = 0; i < num_subtasks && subtasks != nullptr; ++i)
-        if (subtasks[i].level != OC_LEVEL0 && !rollout)
-            return fail(OC_EINVAL, "subtask %d: only oc_rollout takes OC_LEVEL1", i);
-    if (num_subtasks < 1 || num_subtasks > OC_MAX_SUBTASKS) return fail(OC_EINVAL, "num_subtasks %d", num_subtasks);
-    if (h->roll.nnodes < 0)
-        return fail(OC_ELEVEL, "reachability graph exceeds %d nodes (a level of more than %d cells)", ocro::kMaxNodesWide,
-                    ocro::kMaxCellsWide);
-    if (h->roll_blob == nullptr) return fail(OC_EHIP, "rollout tables not on the device");
-    R.L = h->roll;
-    R.nsub = num_subtasks;
-    R.blob_words = h->roll.lds_bytes / 4;  // staged in LDS: the whole blob, or the tables before the distances
-    if (R.L.sq_off != 0 && rollout && B > (int64_t)h->cus * kRollBlock) {
-        // The node-to-square table (the blob's tail) shortens the one-agent Merge bound from ~3.8
-        // to 1.1-2.0 us of a wave.  A rollout launch of one round of blocks (the planner's latency
-        // shape) gains (9.03 -> 8.87 us at 4096 rows); past that every rollout block stages 40%
-        // more table for one row per lane (11.16-11.34 -> 11.35-11.51 us at 2^18: tools/rollx.hip,
-        // profiles/r06/pass_i), so larger rollouts search B's approach nodes as before.  The bounds
-        // kernel (many configurations per staged table) gains at every size, 96-97 -> 85 us at C5,
-        // and the likelihood kernels are unchanged (profiles/r06/pass_w).
-        R.blob_words = R.L.sq_off / 4;
-        R.L.sq_off = 0;
-    }
-    R.pitch = pitch_for(B);
-    R.B = B;
-    for (int i = 0; i < num_subtasks; ++i) {
-        const oc_subtask& s = subtasks[i];
-        if (s.kind < OC_SUB_NONE || s.kind > OC_SUB_DELIVER) return fail(OC_EINVAL, "subtask %d kind %d", i, s.kind);
-        if (s.num_agents < 1 || s.num_agents > 2) return fail(OC_EINVAL, "subtask %d: %d agents", i, s.num_agents);
-        for (int q = 0; q < s.num_agents; ++q)
-            if (s.agent[q] >= h->A) return fail(OC_EINVAL, "subtask %d: agent %d", i, s.agent[q]);
-        if (s.num_agents == 2 && s.agent[0] >= s.agent[1]) return fail(OC_EINVAL, "subtask %d: agents not ascending", i);
-        ocro::Sub& d = R.subs[i];
-        d.kind = s.kind;
-        d.n = s.num_agents;
-        d.agent[0] = s.agent[0];
-        d.agent[1] = s.num_agents == 2 ? s.agent[1] : s.agent[0];
-        d.start[0] = s.start_mask[0];
-        d.start[1] = s.start_mask[1];
-        if (s.level > OC_LEVEL1) return fail(OC_EINVAL, "subtask %d: level %d", i, s.level);
-        d.goal = s.goal_mask;
-        d.count = s.goal_count;
-        d.level = s.level;
-        d.pad = 0;
-    }
-    return OC_OK;
-}
-
-// The planner kernels stage the level's table blob in dynamic LDS.  Past the 64 KB a launch gets
-// by default (graphs of more than ~245 nodes) the kernel must be allowed more, up to the CU's
-// 160 KB; the kernel's static LDS counts against the same limit.
-constexpr int kLdsPerCu = 160 * 1024;
-static int allow_dyn_lds(const void* kernel, int dyn) {
-    if (dyn <= 48 * 1024) return OC_OK;
-    hipFuncAttributes fa;
-    if (hipFuncGetAttributes(&fa, kernel) != hipSuccess) return hip_check("hipFuncGetAttributes");
-    if ((int64_t)fa.sharedSizeBytes + dyn > kLdsPerCu)
-        return fail(OC_ELEVEL, "level tables (%d B) and the kernel's LDS (%d B) exceed %d B", dyn,
-                    (int)fa.sharedSizeBytes, kLdsPerCu);
-    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, dyn) != hipSuccess)
-        return hip_check("hipFuncSetAttribute");
-    return OC_OK;
+    return split_steps(NP, L.pitch, h->A, state_in, state_out, actions, traj, exec_actions, coll_mask, n,
+                       [&](const StepLaunch& l) {
+        return dispatch_step(h, [&](auto a, auto k, auto mode) {
+            constexpr bool kLW = use_loader_wave<a(), k(), mode()>();
+            const int64_t cap = (int64_t)h->cus * (kLW ? 4 : 5);
+            const dim3 grid((unsigned)(need < cap ? need : cap));
+            hipLaunchKernelGGL((oc_step_n_kernel<a(), k(), kCPnt, 0, mode()>), grid, dim3(kBlock + (kLW ? 64 : 0)), 0, s,
+                               L, l.src, l.so, l.ac, l.tr, l.ex, l.cm, stats, l.last ? totals : nullptr, rows, l.m);
+            return hip_check("oc_step_n launch");
+        });
+    });
 }
 
 int oc_rollout(const oc_handle* h, const void* state_in, void* state_out, const uint8_t* actions,
@@ -2736,27 +2748,21 @@ int oc_rollout(const oc_handle* h, const void* state_in, void* state_out, const 
     if (!h->wide && !h->roll.dist_global && B * kRollGroup <= (int64_t)h->cus * kRollBlock) {
         // one round of blocks with a lane group per row (oc_rollout_group_kernel)
         const dim3 ggrid((unsigned)((B * kRollGroup + kRollBlock - 1) / kRollBlock));
-#define OC_LAUNCH_ROLL_GROUP(A, K)                                                                                  \
-    if (const int rc = allow_dyn_lds((const void*)oc_rollout_group_kernel<A, K>, R.blob_words * 4)) return rc;        \
-    hipLaunchKernelGGL((oc_rollout_group_kernel<A, K>), ggrid, dim3(kRollBlock), R.blob_words * 4, st, R,            \
-                       (const uint8_t*)state_in, (uint8_t*)state_out, actions, alloc, h->roll_blob, out_flags, lower_bound)
-        OC_DISPATCH(h->A, h->K, OC_LAUNCH_ROLL_GROUP)
-#undef OC_LAUNCH_ROLL_GROUP
-        return hip_check("oc_rollout launch");
+        return dispatch_ak(h->A, h->K, [&](auto a, auto k) {
+            const auto kernel = oc_rollout_group_kernel<a(), k()>;
+            if (const int rc = allow_dyn_lds((const void*)kernel, R.blob_words * 4)) return rc;
+            hipLaunchKernelGGL(kernel, ggrid, dim3(kRollBlock), R.blob_words * 4, st, R, (const uint8_t*)state_in,
+                               (uint8_t*)state_out, actions, alloc, h->roll_blob, out_flags, lower_bound);
+            return hip_check("oc_rollout launch");
+        });
     }
-#define OC_LAUNCH_ROLL(A, K, W, GD)                                                                             \
-    if (const int rc = allow_dyn_lds((const void*)oc_rollout_kernel<A, K, W, GD>, R.blob_words * 4)) return rc;   \
-    hipLaunchKernelGGL((oc_rollout_kernel<A, K, W, GD>), grid, dim3(kRollBlock), R.blob_words * 4, st, R,            \
-                       (const uint8_t*)state_in, (uint8_t*)state_out, actions, alloc, h->roll_blob, out_flags,       \
-                       lower_bound)
-#define OC_PLAN_WIDE(A, K) OC_LAUNCH_ROLL(A, K, true, true)
-#define OC_PLAN_NARROW_GD(A, K) OC_LAUNCH_ROLL(A, K, false, true)
-#define OC_PLAN_NARROW(A, K) OC_LAUNCH_ROLL(A, K, false, false)
-    OC_DISPATCH_PLAN(h, OC_LAUNCH_ROLL)
-#undef OC_PLAN_WIDE
-#undef OC_PLAN_NARROW_GD
-#undef OC_PLAN_NARROW
-    return hip_check("oc_rollout launch");
+    return dispatch_plan(h, [&](auto a, auto k, auto w, auto gd) {
+        const auto kernel = oc_rollout_kernel<a(), k(), w(), gd()>;
+        if (const int rc = allow_dyn_lds((const void*)kernel, R.blob_words * 4)) return rc;
+        hipLaunchKernelGGL(kernel, grid, dim3(kRollBlock), R.blob_words * 4, st, R, (const uint8_t*)state_in,
+                           (uint8_t*)state_out, actions, alloc, h->roll_blob, out_flags, lower_bound);
+        return hip_check("oc_rollout launch");
+    });
 }
 
 int oc_nav_likelihood(const oc_handle* h, const void* state, const uint8_t* taken, const uint8_t* alloc,
@@ -2786,29 +2792,18 @@ int oc_nav_likelihood(const oc_handle* h, const void* state, const uint8_t* take
     const int64_t need = (B + rows_per_block - 1) / rows_per_block, cap = (int64_t)h->cus * (any_joint ? 16 : 8);
     const dim3 grid((unsigned)(need < cap ? need : cap));
     hipStream_t st = (hipStream_t)stream;
-#define OC_LIK_GO(KERN, A, K, GG, W, GD)                                                                             \
-    do {                                                                                                             \
-        if (const int rc = allow_dyn_lds((const void*)KERN<A, K, GG, W, GD>, R.blob_words * 4)) return rc;          \
-        hipLaunchKernelGGL((KERN<A, K, GG, W, GD>), grid, dim3(kBlock), R.blob_words * 4, st, R, (const uint8_t*)state, \
-                           taken, alloc, h->roll_blob, self_agent, beta, none_action_prob, likelihood, out_flags);   \
-    } while (0)
-#define OC_LAUNCH_LIK(A, K, W, GD)                                                                                   \
-    if (compact && any_joint)                                                                                        \
-        OC_LIK_GO(oc_likelihood_compact_kernel, A, K, 32, W, GD);                                                    \
-    else if (compact)                                                                                                \
-        OC_LIK_GO(oc_likelihood_compact_kernel, A, K, 8, W, GD);                                                     \
-    else if (any_joint)                                                                                              \
-        OC_LIK_GO(oc_likelihood_kernel, A, K, 32, W, GD);                                                            \
-    else                                                                                                             \
-        OC_LIK_GO(oc_likelihood_kernel, A, K, 8, W, GD)
-#define OC_PLAN_WIDE(A, K) OC_LAUNCH_LIK(A, K, true, true)
-#define OC_PLAN_NARROW_GD(A, K) OC_LAUNCH_LIK(A, K, false, true)
-#define OC_PLAN_NARROW(A, K) OC_LAUNCH_LIK(A, K, false, false)
-    OC_DISPATCH_PLAN(h, OC_LAUNCH_LIK)
-#undef OC_PLAN_WIDE
-#undef OC_PLAN_NARROW_GD
-#undef OC_PLAN_NARROW
-    return hip_check("oc_nav_likelihood launch");
+    return dispatch_plan(h, [&](auto a, auto k, auto w, auto gd) {
+        auto go = [&](auto kernel) {
+            if (const int rc = allow_dyn_lds((const void*)kernel, R.blob_words * 4)) return rc;
+            hipLaunchKernelGGL(kernel, grid, dim3(kBlock), R.blob_words * 4, st, R, (const uint8_t*)state, taken, alloc,
+                               h->roll_blob, self_agent, beta, none_action_prob, likelihood, out_flags);
+            return hip_check("oc_nav_likelihood launch");
+        };
+        if (compact && any_joint) return go(oc_likelihood_compact_kernel<a(), k(), 32, w(), gd()>);
+        if (compact) return go(oc_likelihood_compact_kernel<a(), k(), 8, w(), gd()>);
+        if (any_joint) return go(oc_likelihood_kernel<a(), k(), 32, w(), gd()>);
+        return go(oc_likelihood_kernel<a(), k(), 8, w(), gd()>);
+    });
 }
 
 // configuration chunks: enough blocks for this many per CU (round 2's sweep, 0.44 ms kernels:
@@ -2839,18 +2834,13 @@ int oc_subtask_bounds(const oc_handle* h, const void* state, const oc_subtask* s
     if (chunks < 1) chunks = 1;
     const dim3 grid((unsigned)bx, (unsigned)chunks);
     hipStream_t st = (hipStream_t)stream;
-#define OC_LAUNCH_BOUNDS(A, K, W, GD)                                                                         \
-    if (const int rc = allow_dyn_lds((const void*)oc_bounds_kernel<A, K, W, GD>, R.blob_words * 4)) return rc;  \
-    hipLaunchKernelGGL((oc_bounds_kernel<A, K, W, GD>), grid, dim3(kBlock), R.blob_words * 4, st, R,           \
-                       (const uint8_t*)state, h->roll_blob, lower_bound, doable)
-#define OC_PLAN_WIDE(A, K) OC_LAUNCH_BOUNDS(A, K, true, true)
-#define OC_PLAN_NARROW_GD(A, K) OC_LAUNCH_BOUNDS(A, K, false, true)
-#define OC_PLAN_NARROW(A, K) OC_LAUNCH_BOUNDS(A, K, false, false)
-    OC_DISPATCH_PLAN(h, OC_LAUNCH_BOUNDS)
-#undef OC_PLAN_WIDE
-#undef OC_PLAN_NARROW_GD
-#undef OC_PLAN_NARROW
-    return hip_check("oc_subtask_bounds launch");
+    return dispatch_plan(h, [&](auto a, auto k, auto w, auto gd) {
+        const auto kernel = oc_bounds_kernel<a(), k(), w(), gd()>;
+        if (const int rc = allow_dyn_lds((const void*)kernel, R.blob_words * 4)) return rc;
+        hipLaunchKernelGGL(kernel, grid, dim3(kBlock), R.blob_words * 4, st, R, (const uint8_t*)state, h->roll_blob,
+                           lower_bound, doable);
+        return hip_check("oc_subtask_bounds launch");
+    });
 }
 
 int oc_render(const oc_handle* h, const void* state, const uint32_t* atlas, const uint32_t* background,
@@ -2898,36 +2888,11 @@ int oc_render_ordered(const oc_handle* h, const void* state, const uint8_t* draw
     R.parts = 2;  // two blocks per (env, cell row): 0.198 vs 0.214 ms per 1,024 images (3 or 4: 0.211-0.213)
     const dim3 grid((unsigned)(B * H * R.parts));
     hipStream_t st = (hipStream_t)stream;
-#define OC_LAUNCH_RENDER(A, K, WD)                                                                               \
-    hipLaunchKernelGGL((oc_render_kernel<A, K, WD>), grid, dim3(kBlock), 0, st, R, (const uint8_t*)state, draw_rank, \
-                       atlas, background, out)
-    OC_DISPATCH_W(h, OC_LAUNCH_RENDER)
-    return hip_check("oc_render launch");
-}
-
-// oc_observe / oc_cpu_observe: the arguments both check, and the level's side of ObsArgs
-static int observe_args(const oc_handle* h, const void* state, const void* obs, const uint8_t* action_mask,
-                        int32_t dtype, int32_t view_agent, int64_t B, ocob::ObsArgs& R) {
-    if (state == nullptr || B < 0) return fail(OC_EINVAL, "bad argument");
-    if (obs == nullptr && action_mask == nullptr) return fail(OC_EINVAL, "observe: obs and action_mask are both NULL");
-    if (dtype != OC_OBS_U8 && dtype != OC_OBS_F16) return fail(OC_EINVAL, "observe: dtype %d (OC_OBS_U8 or OC_OBS_F16)", dtype);
-    if (view_agent < -1 || view_agent >= h->A)
-        return fail(OC_EINVAL, "observe: view_agent %d outside [-1, %d)", view_agent, h->A);
-    if (((uintptr_t)state & 15u) || ((uintptr_t)action_mask & 3u) || (dtype == OC_OBS_F16 && ((uintptr_t)obs & 1u)))
-        return fail(OC_EINVAL, "misaligned buffer");
-    R = ocob::ObsArgs{};
-    R.W = h->level.width;
-    R.H = h->level.height;
-    R.HW = R.W * R.H;
-    R.C = OC_OBS_CHANNELS(h->A);
-    R.CHW = R.C * R.HW;
-    R.counts = h->level.encoding == OC_ENC_COUNTS;
-    R.rot = view_agent < 0 ? 0 : view_agent;
-    R.nstatic = h->obs_nstatic;
-    R.nt = h->obs_nt;
-    R.pitch = pitch_for(B);
-    R.B = B;
-    return OC_OK;
+    return dispatch_w(h, [&](auto a, auto k, auto w) {
+        hipLaunchKernelGGL((oc_render_kernel<a(), k(), w()>), grid, dim3(kBlock), 0, st, R, (const uint8_t*)state,
+                           draw_rank, atlas, background, out);
+        return hip_check("oc_render launch");
+    });
 }
 
 int oc_observe(const oc_handle* h, const void* state, void* obs, uint8_t* action_mask, int32_t dtype,
@@ -2941,7 +2906,7 @@ int oc_observe(const oc_handle* h, const void* state, void* obs, uint8_t* action
     if (B == 0) return OC_OK;
     // envs per tile: the largest power of two whose tile and staging fit the LDS budget (a 7x7
     // kitchen: 64; the largest wide levels: 1, every tile then with a head and a tail)
-    const int planes = 3 * h->A + (h->wide ? 3 : 2) * h->K;
+    const int planes = ocly::layout(h->A, h->K, h->wide).T;  // the planes before t
     int E = h->obs_tile, lg = 31 - __builtin_clz((unsigned)h->obs_tile), lds = 0;
     for (;; E >>= 1, --lg) {
         R.lds_state = (E * R.CHW + 16 + 15) & ~15;
@@ -2963,16 +2928,15 @@ int oc_observe(const oc_handle* h, const void* state, void* obs, uint8_t* action
     hipStream_t st = (hipStream_t)stream;
     const uint8_t* tab = h->obs_tab;
     const uint16_t* statics = (const uint16_t*)(h->obs_tab + h->obs_static_off);
-#define OC_LAUNCH_OBS(A, K, WD)                                                                                   \
-    if (dtype == OC_OBS_F16)                                                                                      \
-        hipLaunchKernelGGL((ocob::oc_observe_kernel<A, K, WD, true>), grid, dim3(ocob::kBlock), lds, st, R,       \
-                           (const uint8_t*)state, tab, statics, (uint8_t*)obs, action_mask);                      \
-    else                                                                                                          \
-        hipLaunchKernelGGL((ocob::oc_observe_kernel<A, K, WD, false>), grid, dim3(ocob::kBlock), lds, st, R,      \
-                           (const uint8_t*)state, tab, statics, (uint8_t*)obs, action_mask)
-    OC_DISPATCH_W(h, OC_LAUNCH_OBS)
-#undef OC_LAUNCH_OBS
-    return hip_check("oc_observe launch");
+    return dispatch_w(h, [&](auto a, auto k, auto w) {
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(ocob::kBlock), lds, st, R, (const uint8_t*)state, tab, statics,
+                               (uint8_t*)obs, action_mask);
+            return hip_check("oc_observe launch");
+        };
+        return dtype == OC_OBS_F16 ? go(ocob::oc_observe_kernel<a(), k(), w(), true>)
+                                   : go(ocob::oc_observe_kernel<a(), k(), w(), false>);
+    });
 }
 
 int oc_cpu_observe(const oc_handle* h, const void* state, void* obs, uint8_t* action_mask, int32_t dtype,
@@ -2982,63 +2946,17 @@ int oc_cpu_observe(const oc_handle* h, const void* state, void* obs, uint8_t* ac
     ocob::ObsArgs R;
     if (const int rc = observe_args(h, state, obs, action_mask, dtype, view_agent, B, R)) return rc;
     if (B == 0) return OC_OK;
-    if (nthreads == 0) nthreads = (int32_t)std::thread::hardware_concurrency();
-    int64_t nt = nthreads < 1 ? 1 : nthreads;
-    if (nt > (B + 16383) / 16384) nt = (B + 16383) / 16384;  // >= 16 Ki envs per thread
-    if (nt < 1) nt = 1;
+    const int64_t nt = host_threads(nthreads, B, 16384);  // >= 16 Ki envs per thread
     const uint8_t* tab = h->obs_tab_host.data();
     const uint16_t* statics = (const uint16_t*)(tab + h->obs_static_off);
-    auto run = [&](int64_t i) {
+    return run_ranges(nt, [&](int64_t i) {
         const int64_t e0 = B * i / nt, e1 = B * (i + 1) / nt;
-#define OC_CPU_OBS(A, K, WD) \
-    ocob::cpu_observe_range<A, K, WD>(R, tab, statics, (const uint8_t*)state, obs, action_mask, dtype == OC_OBS_F16, e0, e1)
-        OC_DISPATCH_W(h, OC_CPU_OBS)
-#undef OC_CPU_OBS
-        return OC_OK;
-    };
-    // ranges 1..nt-1 on workers, range 0 (and any whose thread cannot start) on the calling thread
-    std::vector<std::thread> pool;
-    int64_t started = 1;
-    try {
-        for (; started < nt; ++started) pool.emplace_back([&, i = started] { (void)run(i); });
-    } catch (const std::exception&) {
-    }
-    const int rc = run(0);
-    for (int64_t i = started; i < nt; ++i) (void)run(i);
-    for (auto& t : pool) t.join();
-    return rc;
-}
-
-// oc_progress / oc_cpu_progress: the arguments both check, and the call's ProgArgs
-static int progress_args(const oc_handle* h, const void* state_prev, const void* states, int32_t n,
-                         const oc_subtask* subtasks, int32_t num_subtasks, const float* weights, const uint8_t* counts,
-                         const uint8_t* events, const float* reward, int64_t B, ocpg::ProgArgs& R) {
-    if (state_prev == nullptr || states == nullptr || subtasks == nullptr || B < 0) return fail(OC_EINVAL, "bad argument");
-    if (n < 1) return fail(OC_EINVAL, "progress: n = %d (at least 1)", n);
-    if (num_subtasks < 1 || num_subtasks > OC_MAX_SUBTASKS)
-        return fail(OC_EINVAL, "progress: num_subtasks %d outside [1, %d]", num_subtasks, OC_MAX_SUBTASKS);
-    if (counts == nullptr && events == nullptr && reward == nullptr)
-        return fail(OC_EINVAL, "progress: counts, events and reward are all NULL");
-    if (((uintptr_t)state_prev & 3u) || ((uintptr_t)states & 3u) || ((uintptr_t)counts & 3u) ||
-        ((uintptr_t)events & 3u) || ((uintptr_t)reward & 15u))
-        return fail(OC_EINVAL, "misaligned buffer");
-    R = ocpg::ProgArgs{};
-    for (int i = 0; i < num_subtasks; ++i) {
-        const int32_t kind = subtasks[i].kind;
-        if (kind != OC_SUB_NONE && kind != OC_SUB_CHOP && kind != OC_SUB_MERGE && kind != OC_SUB_DELIVER)
-            return fail(OC_EINVAL, "progress: subtask %d has kind %d", i, kind);
-        R.sub[i] = (uint32_t)kind << 8 | subtasks[i].goal_mask;
-        R.weight[i] = weights != nullptr ? weights[i] : 1.0f;
-    }
-    R.W = h->level.width;
-    R.tile_words = (h->level.width * h->level.height + 3) / 4;
-    R.n = n;
-    R.S = num_subtasks;
-    R.planes = OC_PROGRESS_EVENT_PLANES(num_subtasks);
-    R.pitch = pitch_for(B);
-    R.B = B;
-    R.state_bytes = (int64_t)(3 * h->A + (h->wide ? 3 : 2) * h->K + 3) * R.pitch;
-    return OC_OK;
+        return dispatch_w(h, [&](auto a, auto k, auto w) {
+            ocob::cpu_observe_range<a(), k(), w()>(R, tab, statics, (const uint8_t*)state, obs, action_mask,
+                                                   dtype == OC_OBS_F16, e0, e1);
+            return OC_OK;
+        });
+    });
 }
 
 int oc_progress(const oc_handle* h, const void* state_prev, const void* states, int32_t n, const oc_subtask* subtasks,
@@ -3056,12 +2974,11 @@ int oc_progress(const oc_handle* h, const void* state_prev, const void* states, 
     const int64_t lanes = (B + 3) / 4;
     const dim3 grid((unsigned)((lanes + ocpg::kBlock - 1) / ocpg::kBlock));
     hipStream_t st = (hipStream_t)stream;
-#define OC_LAUNCH_PROG(A, K, WD)                                                                              \
-    hipLaunchKernelGGL((ocpg::oc_progress_kernel<A, K, WD>), grid, dim3(ocpg::kBlock), 0, st, R, h->obs_tab, \
-                       (const uint8_t*)state_prev, (const uint8_t*)states, counts, events, reward)
-    OC_DISPATCH_W(h, OC_LAUNCH_PROG)
-#undef OC_LAUNCH_PROG
-    return hip_check("oc_progress launch");
+    return dispatch_w(h, [&](auto a, auto k, auto w) {
+        hipLaunchKernelGGL((ocpg::oc_progress_kernel<a(), k(), w()>), grid, dim3(ocpg::kBlock), 0, st, R, h->obs_tab,
+                           (const uint8_t*)state_prev, (const uint8_t*)states, counts, events, reward);
+        return hip_check("oc_progress launch");
+    });
 }
 
 int oc_cpu_progress(const oc_handle* h, const void* state_prev, const void* states, int32_t n,
@@ -3073,33 +2990,18 @@ int oc_cpu_progress(const oc_handle* h, const void* state_prev, const void* stat
     if (const int rc = progress_args(h, state_prev, states, n, subtasks, num_subtasks, weights, counts, events, reward, B, R))
         return rc;
     if (B == 0) return OC_OK;
-    if (nthreads == 0) nthreads = (int32_t)std::thread::hardware_concurrency();
-    int64_t nt = nthreads < 1 ? 1 : nthreads;
-    if (nt > (B + 16383) / 16384) nt = (B + 16383) / 16384;  // >= 16 Ki envs per thread
-    if (nt < 1) nt = 1;
+    const int64_t nt = host_threads(nthreads, B, 16384);  // >= 16 Ki envs per thread
     uint8_t tab[ocpg::kTableBytes];
     ocpg::build_table(h->obs_tab_host.data(), R.tile_words, tab);
     const int64_t words = (B + 3) / 4;
-    auto run = [&](int64_t i) {
+    return run_ranges(nt, [&](int64_t i) {
         const int64_t g0 = words * i / nt, g1 = words * (i + 1) / nt;
-#define OC_CPU_PROG(A, K, WD)                                                                                      \
-    ocpg::cpu_progress_words<A, K, WD>(R, tab, (const uint8_t*)state_prev, (const uint8_t*)states, counts, events, \
-                                       reward, g0, g1)
-        OC_DISPATCH_W(h, OC_CPU_PROG)
-#undef OC_CPU_PROG
-        return OC_OK;
-    };
-    // ranges 1..nt-1 on workers, range 0 (and any whose thread cannot start) on the calling thread
-    std::vector<std::thread> pool;
-    int64_t started = 1;
-    try {
-        for (; started < nt; ++started) pool.emplace_back([&, i = started] { (void)run(i); });
-    } catch (const std::exception&) {
-    }
-    const int rc = run(0);
-    for (int64_t i = started; i < nt; ++i) (void)run(i);
-    for (auto& t : pool) t.join();
-    return rc;
+        return dispatch_w(h, [&](auto a, auto k, auto w) {
+            ocpg::cpu_progress_words<a(), k(), w()>(R, tab, (const uint8_t*)state_prev, (const uint8_t*)states, counts,
+                                                    events, reward, g0, g1);
+            return OC_OK;
+        });
+    });
 }
 
 int oc_gen_actions(const oc_handle* h, uint8_t* actions, int64_t B, int64_t env_offset, int64_t step,
@@ -3122,37 +3024,12 @@ int oc_state_checksum(const oc_handle* h, const void* state, int64_t B, uint64_t
     if (hipMemsetAsync(out, 0, sizeof(uint64_t), s) != hipSuccess) return hip_check("oc_state_checksum memset");
     if (B == 0) return OC_OK;
     const int64_t P = pitch_for(B);
-    const int np = 3 * h->A + (h->wide ? 3 : 2) * h->K + 3;
     const dim3 grid((unsigned)(P / kEnvsPerBlock));
-#define OC_CK(NP) hipLaunchKernelGGL((oc_checksum_kernel<NP>), grid, dim3(kBlock), 0, s, (const uint8_t*)state, P, B, (unsigned long long*)out)
-    switch (np) {
-        case 17: OC_CK(17); break;   // A=2 K=4
-        case 14: OC_CK(14); break;   // A=1 K=4
-        case 20: OC_CK(20); break;   // A=3 K=4
-        case 23: OC_CK(23); break;   // A=4 K=4
-        case 22: OC_CK(22); break;   // A=1 K=8
-        case 25: OC_CK(25); break;   // A=2 K=8
-        case 28: OC_CK(28); break;   // A=3 K=8
-        case 31: OC_CK(31); break;   // A=4 K=8
-        case 38: OC_CK(38); break;   // A=1 K=16
-        case 41: OC_CK(41); break;   // A=2 K=16
-        case 44: OC_CK(44); break;   // A=3 K=16
-        case 47: OC_CK(47); break;   // A=4 K=16
-        case 18: OC_CK(18); break;   // wide: A=1 K=4
-        case 21: OC_CK(21); break;   // wide: A=2 K=4
-        case 24: OC_CK(24); break;   // wide: A=3 K=4
-        case 27: OC_CK(27); break;   // wide: A=4 K=4
-        case 30: OC_CK(30); break;   // wide: A=1 K=8
-        case 33: OC_CK(33); break;   // wide: A=2 K=8
-        case 36: OC_CK(36); break;   // wide: A=3 K=8
-        case 39: OC_CK(39); break;   // wide: A=4 K=8
-        case 54: OC_CK(54); break;   // wide: A=1 K=16
-        case 57: OC_CK(57); break;   // wide: A=2 K=16
-        case 60: OC_CK(60); break;   // wide: A=3 K=16
-        case 63: OC_CK(63); break;   // wide: A=4 K=16
-        default: return fail(OC_EINVAL, "unsupported plane count %d", np);
-    }
-    return hip_check("oc_state_checksum launch");
+    return dispatch_w(h, [&](auto a, auto k, auto w) {
+        hipLaunchKernelGGL((oc_checksum_kernel<Planes<a(), k(), w()>::NP>), grid, dim3(kBlock), 0, s,
+                           (const uint8_t*)state, P, B, (unsigned long long*)out);
+        return hip_check("oc_state_checksum launch");
+    });
 }
 
 int oc_stats_size(const oc_handle* h, int64_t B, int64_t* nbytes) {

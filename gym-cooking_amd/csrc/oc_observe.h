@@ -20,6 +20,7 @@
 #include <cstring>
 
 #include "../../include/oc_engine.h"
+#include "oc_layout.h"
 
 #define OC_OH __host__ __device__ inline __attribute__((always_inline))
 
@@ -72,12 +73,7 @@ OC_OH bool mergeable(uint32_t a, uint32_t b, bool counts) {
                   : !(a & b & OC_M_PLATE) && ((u & 7u) & ~(u >> OC_M_CHOPPED_SHIFT)) == 0u;
 }
 
-// Plane indices of the oc_layout.
-template <int A, int K, bool WIDE>
-struct Planes {
-    static constexpr int X = 0, Y = A, HOLD = 2 * A, LOC = 3 * A, LOC_HI = 3 * A + K, MASK = 3 * A + (WIDE ? 2 : 1) * K;
-    static constexpr int N = MASK + K;  // planes the observation reads (t and flags follow)
-};
+using ocly::Planes;  // the observation reads the planes before T (t and flags follow)
 
 // Whether World.NAV_ACTIONS[k] is in get_single_actions of agent a (navigation_planner/
 // utils.py:55-90): get(plane) reads this env's byte of a plane, tile(cell) the level's OC_TILE_*
@@ -191,9 +187,9 @@ __global__ __launch_bounds__(kBlock) void oc_observe_kernel(ObsArgs R, const uin
     extern __shared__ __attribute__((aligned(16))) uint8_t obs_lds[];
     constexpr int kEs = F16 ? 2 : 1;          // output element size
     constexpr int kV = 16 / kEs;              // elements (LDS bytes) per 16-byte output chunk
-    constexpr int kStage = 4;                 // state words per lane: PL::N * E / 4 <= 60 * 16 words
+    constexpr int kStage = 4;                 // state words per lane: PL::T * E / 4 <= 60 * 16 words
     const int t = (int)threadIdx.x, E = R.tile_envs, lg = R.log2_envs;
-    const int wpe = E >> 2, nw = PL::N * wpe;  // four envs per word (tiles and the pitch are multiples of E)
+    const int wpe = E >> 2, nw = PL::T * wpe;  // four envs per word (tiles and the pitch are multiples of E)
     const int env = t & (E - 1), part = t >> lg, parts = kBlock >> lg;
     const int64_t ntiles = (R.B + E - 1) >> lg;
     uint32_t* tile32 = (uint32_t*)obs_lds;
@@ -237,7 +233,7 @@ __global__ __launch_bounds__(kBlock) void oc_observe_kernel(ObsArgs R, const uin
             for (int r = 0; r < kStage; ++r)
                 if (t + r * kBlock < nw) ((uint32_t*)st)[t + r * kBlock] = sw[r];
         } else {
-            for (int i = t; i < PL::N * E; i += kBlock) st[i] = state[(int64_t)(i >> lg) * R.pitch + env0 + (i & (E - 1))];
+            for (int i = t; i < PL::T * E; i += kBlock) st[i] = state[(int64_t)(i >> lg) * R.pitch + env0 + (i & (E - 1))];
         }
         __syncthreads();
         if (tile + gridDim.x < ntiles) load_state(tile + gridDim.x);  // lands behind this tile's stores

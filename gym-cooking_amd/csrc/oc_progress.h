@@ -28,6 +28,7 @@
 #include <cstring>
 
 #include "../../include/oc_engine.h"
+#include "oc_layout.h"
 #include "oc_swar.h"
 
 namespace ocpg {
@@ -47,12 +48,7 @@ struct ProgArgs {
     float weight[OC_MAX_SUBTASKS];
 };
 
-// Plane indices of the oc_layout.
-template <int A, int K, bool WIDE>
-struct Planes {
-    static constexpr int X = 0, Y = A, HOLD = 2 * A, LOC = 3 * A, LOC_HI = 3 * A + K, MASK = 3 * A + (WIDE ? 2 : 1) * K;
-    static constexpr int T = MASK + K, F = T + 2, NP = F + 1;
-};
+using ocly::Planes;
 
 // What the counts read of one state's four envs: per slot the mask word and two h80 words,
 //   nd : the slot is live and the first live slot of its (cell, mask) -- among the slots whose

@@ -28,7 +28,7 @@ static uint32_t rnd() {
 // count_i of env e, one env at a time (include/oc_engine.h)
 template <int A, int K, bool WIDE>
 static int scalar_count(const uint8_t* s, int64_t P, int64_t e, int W, const uint8_t* tab, int kind, int goal) {
-    using PL = ocpg::Planes<A, K, WIDE>;
+    using PL = ocly::Planes<A, K, WIDE>;
     if (kind == OC_SUB_NONE) return 0;
     int cells[K], n = 0, cnt = 0;
     for (int j = 0; j < K; ++j) {
@@ -51,7 +51,7 @@ static int scalar_count(const uint8_t* s, int64_t P, int64_t e, int W, const uin
 
 template <int A, int K, bool WIDE>
 static int run(int64_t B, int n, int S) {
-    using PL = ocpg::Planes<A, K, WIDE>;
+    using PL = ocly::Planes<A, K, WIDE>;
     const int64_t P = (B + 4095) / 4096 * 4096;
     const int W = WIDE ? 31 : 15, H = WIDE ? 31 : 16, cells = W * H;
     std::vector<uint8_t> tiles((cells + 3) & ~3, 0);
