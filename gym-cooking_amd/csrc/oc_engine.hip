@@ -39,36 +39,29 @@
 #include "oc_observe.h"
 #include "oc_progress.h"
 #include "oc_rollout.h"
+#include "oc_stepio.h"
 #include "oc_swar.h"
 
 namespace {
 
 using ocly::Planes;  // the state's plane layout (oc_layout.h)
+// the step family's chunk, its plane walk, tally and class lookups (oc_stepio.h)
+using ocio::Chunk, ocio::kEPL, ocio::NarrowClass, ocio::StepStats, ocio::WideClass;
 
 constexpr int kBlock = 256;  // 4 waves
 constexpr int kStepBlock = 128;  // oc_step_kernel: 2 waves
-constexpr int kEPL = 4;      // envs per lane: one dword per byte plane
 constexpr int kEnvsPerBlock = kBlock * kEPL;
 
 // Kernel argument block: everything static about the level, passed by value (SGPRs).
 struct LevelArgs {
     uint32_t cls4[64];    // tile class byte of cell c (ocsw::tile_class) in byte c % 4 of word c / 4;
-                          // cells >= W*H (up to 255, 0xFF = dead) read 0
-    uint64_t dcell_lut;   // per action code: signed cell delta + 128 (byte lanes 0..4)
-    int32_t W, H;
-    int32_t done_cell;    // first Delivery in scan order (done() reads only it, :349)
-    int32_t max_T;        // 0 = no limit
-    uint32_t goals;       // up to 4 goal masks, one per byte
-    int32_t ngoals;
-    uint32_t tmpl_x, tmpl_y;          // spawn x / y of agents 0..3, one per byte
-    uint32_t tmpl_cell[4], tmpl_mask[4];  // item slots 0..15, one per byte
+                          // cells >= W*H (up to 255, 0xFF = dead) read 0; all 0 on a wide level
     int64_t pitch;
     int64_t B;
     ocsw::SwarLevel sw;  // replicated constants / LUTs of the SWAR step
 };
 
 __device__ __forceinline__ uint32_t byte_of(uint32_t w, int j) { return (w >> (8 * j)) & 0xFFu; }
-__device__ __forceinline__ uint32_t byte_of4(const uint32_t (&w)[4], int j) { return byte_of(w[j >> 2], j & 3); }
 
 // Statistics partial sums, one row of OC_NSTATS uint64 per block.  Wave sum over DPP (VALU
 // lane moves, no LDS round trips): an inclusive scan inside each 16-lane row (row_shr 1, 2,
@@ -87,14 +80,6 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 // Wave-uniform "some env of the wave": the step's rare-event split (ocsw::step4).
 struct WaveAny {
     __device__ __forceinline__ bool operator()(uint32_t v) const { return __ballot(v != 0u) != 0ull; }
-};
-
-// One lane's slice of the batch: kEPL consecutive envs, one dword per byte plane.
-template <int A, int K>
-struct Chunk {
-    uint32_t wx[A], wy[A], wh[A], wa[A], wl[K], wm[K];
-    uint2 wt;
-    uint32_t wf;
 };
 
 // Buffer resources of one launch: every plane access is a buffer load/store with the lane's
@@ -129,6 +114,15 @@ __device__ __forceinline__ void bst32(__amdgpu_buffer_rsrc_t r, uint32_t v, uint
     __builtin_amdgcn_raw_buffer_store_b32(v, r, (int)voff, (int)soff, CP);
 }
 
+// The three step kernels, oc_step_kernel (step_chunk), oc_step_n_kernel and oc_step_wide_kernel,
+// keep their own load, store walks, tally, descriptors and statistics flush, written out as they
+// were before oc_stepio.h: taking them from shared code (the walks, one descriptor helper, one flush,
+// StepStats::add) changed register allocation and schedule although the stores, their order and the
+// wait-free loop were the same (oc_step_n_kernel throughout, once with a spill in the loader-wave
+// build; four oc_step_kernel builds), and the wide kernel measured 2-3 % slower over them
+// (profiles/step_chunk_refactor/).  Their instruction text is equal to the earlier kernels'.  The
+// reset kernel and oc_cpu_step use the shared pieces; what must stay in step with them is the plane
+// order of ocio::load / ocio::store.
 template <int A, int K, bool kActs = true>
 __device__ __forceinline__ void load_chunk(Chunk<A, K>& c, const Bufs& b, uint32_t P, uint32_t g) {
     using PL = Planes<A, K, false>;
@@ -146,15 +140,10 @@ __device__ __forceinline__ void load_chunk(Chunk<A, K>& c, const Bufs& b, uint32
         c.wm[j] = bld32(b.sin, vo, (PL::MASK + j) * P);
     }
     const auto t = __builtin_amdgcn_raw_buffer_load_b64(b.sin, (int)(g * 8u), (int)(PL::T * P), 0);
-    c.wt = make_uint2(t[0], t[1]);
+    c.t0 = t[0];
+    c.t1 = t[1];
     c.wf = bld32(b.sin, vo, PL::F * P);
 }
-
-// Per-lane episode counters; at the end of the kernel a wave sums them and lane 0 adds them
-// to the block's stats row with no-return 64-bit atomics.
-struct StepStats {
-    uint32_t eps = 0u, succ = 0u, err = 0u, coll = 0u, steps = 0u;
-};
 
 // Step the kEPL envs of chunk c (SWAR, oc_swar.h) and store every output plane word of lane g.
 template <int A, int K, int CP = 0, int MODE = 1>
@@ -167,7 +156,7 @@ __device__ __forceinline__ void step_chunk(const LevelArgs& L, const uint8_t* tb
         return b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
     };
     const uint32_t f_in = c.wf;
-    uint32_t T0 = c.wt.x, T1 = c.wt.y, ex[A], cm;
+    uint32_t T0 = c.t0, T1 = c.t1, ex[A], cm;
     uint32_t pending = ocsw::at_done80<K, MODE>(L.sw, c.wl);  // a loaded state: the full path once
     const bool full = ocsw::step4<A, K, MODE>(L.sw, c.wx, c.wy, c.wh, c.wl, c.wm, T0, T1, c.wf, c.wa, ex, cm,
                                               cls_of, WaveAny{}, pending);
@@ -396,7 +385,7 @@ __global__ __launch_bounds__(kBlock + (LW ? 64 : 0), LW ? 5 : 1) void oc_step_n_
         // every step's stores (an s_waitcnt the compiler's waitcnt pass sees and accounts for)
         if (LW) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), expcnt / lgkmcnt untouched
         const uint32_t vo = g * 4u;
-        uint32_t T0 = c.wt.x, T1 = c.wt.y, nxt[A];
+        uint32_t T0 = c.t0, T1 = c.t1, nxt[A];
         uint32_t pending = ocsw::at_done80<K, MODE>(L.sw, c.wl);  // the loaded state: the full path once
         const int64_t rem = L.B - (int64_t)g * kEPL;
         const uint32_t vmask = rem >= kEPL ? 0xFFFFFFFFu : (rem <= 0 ? 0u : (1u << (8 * (uint32_t)rem)) - 1u);
@@ -1278,12 +1267,10 @@ __global__ __launch_bounds__(kBlock) void oc_bounds_kernel(RollArgs R, const uin
 // ---- wide levels (more than 255 cells: u16 cell ids) ----------------------------------------
 // A wide level (more than 255 cells, u16 cell ids) is stepped by ocsw::step4w: the SWAR step
 // with every cell-valued quantity as two byte words (its low and high bytes, the wide layout's
-// two item-cell planes), four envs per lane like oc_step_n_kernel (round 6; rounds 4-5 ran the
-// scalar RowOps::env_step, one env after another).  Such levels are user kitchens; the shipped
-// ones are all narrow.
+// two item-cell planes), four envs per lane like oc_step_n_kernel.  Such levels are user kitchens;
+// the shipped ones are all narrow.  Its kernel takes no 256-byte narrow class table (LevelArgs::cls4):
+// the classes come from the level's tile table in device memory.
 struct WideArgs {
-    ocro::RollLevel L;   // W, H, enc; tile_off 0: the table below
-    ocro::StepLevel S;
     ocsw::SwarLevel sw;  // the SWAR step's constants (step4w reads the wide fields)
     int32_t tile_words;  // the tile table's words (W * H bytes rounded up to 4)
     int64_t pitch, B;
@@ -1418,28 +1405,6 @@ __global__ __launch_bounds__(kBlock) void oc_step_wide_kernel(WideArgs R, const 
                 if (v[c]) atomicAdd(row + c, (unsigned long long)v[c]);
         }
     }
-}
-
-// reset() of a wide level: the template in every env of the pitch
-template <int A, int K>
-__global__ __launch_bounds__(kBlock) void oc_reset_wide_kernel(WideArgs R, uint8_t* __restrict__ s) {
-    using PL = Planes<A, K, true>;
-    const int64_t P = R.pitch, e = blockIdx.x * (int64_t)kBlock + threadIdx.x;
-    if (e >= P) return;
-#pragma unroll
-    for (int a = 0; a < A; ++a) {
-        s[a * P + e] = R.S.spawn_x[a];
-        s[(PL::Y + a) * P + e] = R.S.spawn_y[a];
-        s[(PL::HOLD + a) * P + e] = (uint8_t)OC_HOLD_NONE;
-    }
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        s[(PL::LOC + j) * P + e] = (uint8_t)R.S.item_cell[j];
-        s[(PL::LOC_HI + j) * P + e] = (uint8_t)(R.S.item_cell[j] >> 8);
-        s[(PL::MASK + j) * P + e] = R.S.item_mask[j];
-    }
-    ((uint16_t*)(s + PL::T * P))[e] = 0;
-    s[PL::F * P + e] = 0;
 }
 
 // Image observation (oc_render, GameImage.get_image_obs: gym_cooking/misc/game/gameimage.py:31-51,
@@ -1711,27 +1676,21 @@ __global__ __launch_bounds__(kBlock) void oc_render_kernel(RenderArgs R, const u
     }
 }
 
-// reset(): broadcast the level template (overcooked_environment.py:201-250).
-template <int A, int K>
-__global__ __launch_bounds__(kBlock) void oc_reset_kernel(LevelArgs L, uint8_t* __restrict__ s) {
-    const int64_t P = L.pitch;
-    const int64_t e0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * kEPL;
-    auto rep = [](uint32_t b) { return (b & 0xFFu) * 0x01010101u; };
-    auto st32 = [&](int plane, uint32_t v) { *reinterpret_cast<uint32_t*>(s + plane * P + e0) = v; };
-    using PL = Planes<A, K, false>;
-#pragma unroll
-    for (int a = 0; a < A; ++a) {
-        st32(PL::X + a, rep(byte_of(L.tmpl_x, a)));
-        st32(PL::Y + a, rep(byte_of(L.tmpl_y, a)));
-        st32(PL::HOLD + a, rep(OC_HOLD_NONE));
+// reset(): broadcast the level template (overcooked_environment.py:201-250) over the whole pitch,
+// one chunk per lane through the shared store walk with 64-bit addresses (no 2 GiB limit here).
+struct GlobalWords {
+    uint8_t* s;
+    int64_t P, g;
+    __device__ __forceinline__ void st32(int plane, uint32_t v) const {
+        *reinterpret_cast<uint32_t*>(s + plane * P + 4 * g) = v;
     }
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        st32(PL::LOC + j, rep(byte_of4(L.tmpl_cell, j)));
-        st32(PL::MASK + j, rep(byte_of4(L.tmpl_mask, j)));
+    __device__ __forceinline__ void st64(int plane, uint32_t lo, uint32_t hi) const {
+        *reinterpret_cast<uint2*>(s + plane * P + 8 * g) = make_uint2(lo, hi);
     }
-    *reinterpret_cast<uint2*>(s + PL::T * P + 2 * e0) = make_uint2(0u, 0u);
-    st32(PL::F, 0u);
+};
+template <int A, int K, bool WIDE>
+__global__ __launch_bounds__(kBlock) void oc_reset_kernel(ocsw::SwarLevel sw, int64_t pitch, uint8_t* __restrict__ s) {
+    ocio::store(ocio::template_chunk<A, K, WIDE>(sw), GlobalWords{s, pitch, (int64_t)blockIdx.x * kBlock + threadIdx.x});
 }
 
 // Order-sensitive 64-bit checksum of the state of envs [0, B):
@@ -1848,10 +1807,8 @@ struct oc_handle {
     uint8_t* roll_blob = nullptr;  // device: the level's rollout table blob (oc_rollout.h)
     int32_t roll_blob_bytes = 0;
     std::vector<uint8_t> roll_blob_host;  // the same blob on the host
-    // wide levels (more than 255 cells): the scalar step's tables
+    // wide levels (more than 255 cells, u16 cell ids): the tile table of oc_step_wide_kernel
     bool wide = false;
-    ocro::StepLevel step;
-    ocro::RollLevel step_lv;         // W, H, enc; tile_off 0 (the tile table alone)
     uint8_t* wide_tiles = nullptr;   // device: tile class per cell (W * H rounded up to 4 bytes)
     uint8_t wide_tiles_host[ocro::kMaxCellsWide];
     int32_t lik_form = OC_LIK_FORM_AUTO;  // oc_set_likelihood_form
@@ -1885,161 +1842,6 @@ struct ErrScope {
 int64_t stats_rows(const oc_handle*, int64_t B) {
     const int64_t need = pitch_for(B) / kEnvsPerBlock;
     return need < kStatRows ? need : kStatRows;
-}
-
-// The host step workers' plane word g (4 envs) of a plane, read and written whole.
-static uint32_t rd(const uint8_t* base, int64_t P, int plane, int64_t g) {
-    uint32_t v;
-    memcpy(&v, base + plane * P + 4 * g, 4);
-    return v;
-}
-static void wr(uint8_t* base, int64_t P, int plane, int64_t g, uint32_t v) { memcpy(base + plane * P + 4 * g, &v, 4); }
-
-// The host step workers' statistics: add() tallies one stepped word (its rem = B - 4g envs that
-// count), store() writes a range's row.
-struct HostTally {
-    uint64_t eps = 0, succ = 0, steps = 0, ncoll = 0, err = 0;
-    void add(int64_t rem, bool full, uint32_t f_in, uint32_t F, uint32_t T0, uint32_t T1, uint32_t CM) {
-        const uint32_t vmask = rem >= kEPL ? 0xFFFFFFFFu : (1u << (8 * (uint32_t)rem)) - 1u;
-        ncoll += (uint64_t)__builtin_popcount(CM & vmask);
-        if (!full) return;
-        const uint32_t ended = (F & ~f_in & vmask) & ocsw::k01;
-        for (int q = 0; q < kEPL; ++q) {
-            if (!((ended >> (8 * q)) & 1u)) continue;
-            ++eps;
-            succ += (F >> (8 * q + 1)) & 1u;
-            err += (F >> (8 * q + 2)) & 1u;
-            steps += ((q < 2 ? T0 : T1) >> (16 * (q & 1))) & 0xFFFFu;
-        }
-    }
-    void store(uint64_t* st) const {
-        st[OC_STAT_EPISODES] = eps;
-        st[OC_STAT_SUCCESSES] = succ;
-        st[OC_STAT_STEPS] = steps;
-        st[OC_STAT_COLLISIONS] = ncoll;
-        st[OC_STAT_ERRORS] = err;
-    }
-};
-
-// oc_cpu_step's worker: the host pass of the same SWAR step (oc_swar.h), words [g0, g1) of
-// the batch (4 envs each, as one lane of oc_step_kernel), per-word rare-event split.
-template <int A, int K, int MODE>
-static void cpu_step_words(const oc_handle* h, const uint8_t* sin, uint8_t* sout, const uint8_t* act,
-                           uint8_t* exo, uint8_t* coll, int64_t B, int64_t P, int64_t g0, int64_t g1,
-                           uint64_t* st) {
-    using PL = Planes<A, K, false>;
-    const LevelArgs& L = h->args;
-    const uint8_t* tbl = (const uint8_t*)L.cls4;
-    auto cls_of = [tbl](uint32_t c) -> uint32_t {
-        return (uint32_t)tbl[c & 0xFFu] | ((uint32_t)tbl[(c >> 8) & 0xFFu] << 8) |
-               ((uint32_t)tbl[(c >> 16) & 0xFFu] << 16) | ((uint32_t)tbl[c >> 24] << 24);
-    };
-    HostTally tally;
-    for (int64_t g = g0; g < g1; ++g) {
-        uint32_t X[A], Y[A], Hh[A], Lc[K], M[K], AC[A], EX[A], T0, T1, F, CM;
-        for (int a = 0; a < A; ++a) {
-            X[a] = rd(sin, P, a, g);
-            Y[a] = rd(sin, P, PL::Y + a, g);
-            Hh[a] = rd(sin, P, PL::HOLD + a, g);
-            AC[a] = rd(act, P, a, g);
-        }
-        for (int j = 0; j < K; ++j) {
-            Lc[j] = rd(sin, P, PL::LOC + j, g);
-            M[j] = rd(sin, P, PL::MASK + j, g);
-        }
-        memcpy(&T0, sin + PL::T * P + 8 * g, 4);
-        memcpy(&T1, sin + PL::T * P + 8 * g + 4, 4);
-        F = rd(sin, P, PL::F, g);
-        const uint32_t f_in = F;
-        uint32_t pending = ocsw::at_done80<K, MODE>(L.sw, Lc);
-        const bool full = ocsw::step4<A, K, MODE>(L.sw, X, Y, Hh, Lc, M, T0, T1, F, AC, EX, CM, cls_of,
-                                                  [](uint32_t v) { return v != 0u; }, pending);
-        const int64_t rem = B - g * kEPL;
-        tally.add(rem, full, f_in, F, T0, T1, CM);
-        for (int a = 0; a < A; ++a) {
-            wr(sout, P, a, g, X[a]);
-            wr(sout, P, PL::Y + a, g, Y[a]);
-            wr(sout, P, PL::HOLD + a, g, Hh[a]);
-            if (exo != nullptr) wr(exo, P, a, g, EX[a]);
-        }
-        for (int j = 0; j < K; ++j) {
-            wr(sout, P, PL::LOC + j, g, Lc[j]);
-            wr(sout, P, PL::MASK + j, g, M[j]);
-        }
-        memcpy(sout + PL::T * P + 8 * g, &T0, 4);
-        memcpy(sout + PL::T * P + 8 * g + 4, &T1, 4);
-        wr(sout, P, PL::F, g, F);
-        if (coll != nullptr) wr(coll, P, 0, g, CM);
-    }
-    tally.store(st);
-}
-
-// oc_cpu_step on a wide level: words [g0, g1) (4 envs each) through the host pass of the
-// wide SWAR step (ocsw::step4w), per-word rare-event split, as oc_step_wide_kernel
-template <int A, int K>
-static void cpu_step_wide(const oc_handle* h, const uint8_t* sin, uint8_t* sout, const uint8_t* act, uint8_t* exo,
-                          uint8_t* coll, int64_t B, int64_t P, int64_t g0, int64_t g1, uint64_t* st) {
-    using PL = Planes<A, K, true>;
-    const ocsw::SwarLevel& SL = h->args.sw;
-    uint8_t cls[ocro::kMaxCellsWide];
-    for (int c = 0; c < ocro::kMaxCellsWide; ++c) cls[c] = ocsw::tile_class(h->wide_tiles_host[c]);
-    auto cls_of = [&cls](const ocsw::Cell2& c) -> uint32_t {
-        uint32_t r = 0u;
-        for (int q = 0; q < kEPL; ++q) {
-            const uint32_t idx = ((((c.hi >> (8 * q)) & 0xFFu) << 8) | ((c.lo >> (8 * q)) & 0xFFu)) & 0x3FFu;
-            r |= (uint32_t)cls[idx] << (8 * q);
-        }
-        return r;
-    };
-    HostTally tally;
-    for (int64_t g = g0; g < g1; ++g) {
-        uint32_t X[A], Y[A], Hh[A], LL[K], LH[K], M[K], AC[A], EX[A], T0, T1, F, CM;
-        for (int a = 0; a < A; ++a) {
-            X[a] = rd(sin, P, PL::X + a, g);
-            Y[a] = rd(sin, P, PL::Y + a, g);
-            Hh[a] = rd(sin, P, PL::HOLD + a, g);
-            AC[a] = rd(act, P, a, g);
-        }
-        for (int j = 0; j < K; ++j) {
-            LL[j] = rd(sin, P, PL::LOC + j, g);
-            LH[j] = rd(sin, P, PL::LOC_HI + j, g);
-            M[j] = rd(sin, P, PL::MASK + j, g);
-        }
-        memcpy(&T0, sin + PL::T * P + 8 * g, 4);
-        memcpy(&T1, sin + PL::T * P + 8 * g + 4, 4);
-        F = rd(sin, P, PL::F, g);
-        const uint32_t f_in = F;
-        uint32_t pending = ocsw::at_done80w<K>(SL, LL, LH);
-        const bool full = ocsw::step4w<A, K>(SL, X, Y, Hh, LL, LH, M, T0, T1, F, AC, EX, CM, cls_of,
-                                             [](uint32_t v) { return v != 0u; }, pending);
-        const int64_t rem = B - g * kEPL;
-        tally.add(rem, full, f_in, F, T0, T1, CM);
-        // the batch's last word: only its columns below B are written (a host caller's buffer
-        // may be exactly B bytes per plane past the pitch's start)
-        const int ncol = rem >= kEPL ? kEPL : (int)rem;
-        auto put = [&](uint8_t* base, int plane, uint32_t v) {
-            if (ncol == kEPL) wr(base, P, plane, g, v);
-            else memcpy(base + plane * P + 4 * g, &v, (size_t)ncol);
-        };
-        for (int a = 0; a < A; ++a) {
-            put(sout, PL::X + a, X[a]);
-            put(sout, PL::Y + a, Y[a]);
-            put(sout, PL::HOLD + a, Hh[a]);
-            if (exo != nullptr) put(exo, a, EX[a]);
-        }
-        for (int j = 0; j < K; ++j) {
-            put(sout, PL::LOC + j, LL[j]);
-            put(sout, PL::LOC_HI + j, LH[j]);
-            put(sout, PL::MASK + j, M[j]);
-        }
-        uint8_t tb[8];
-        memcpy(tb, &T0, 4);
-        memcpy(tb + 4, &T1, 4);
-        memcpy(sout + PL::T * P + 8 * g, tb, (size_t)(2 * ncol));
-        put(sout, PL::F, F);
-        if (coll != nullptr) put(coll, 0, CM);
-    }
-    tally.store(st);
 }
 
 // Kernel and worker templates are picked by generic lambdas that take their template arguments as
@@ -2180,18 +1982,6 @@ static int split_steps(int64_t NP, int64_t P, int A, const void* sin, void* sout
     return OC_OK;
 }
 
-// The level's side of a wide kernel's arguments (tile_words 0: a kernel that reads no tiles).
-static WideArgs wide_args(const oc_handle* h, int64_t B, int32_t tile_words) {
-    WideArgs R;
-    R.L = h->step_lv;
-    R.S = h->step;
-    R.sw = h->args.sw;
-    R.tile_words = tile_words;
-    R.pitch = pitch_for(B);
-    R.B = B;
-    return R;
-}
-
 // A level table's device copy, or nullptr (and no HIP error left behind) when there is no device
 // to put it on, e.g. a CPU-only build check: the entry points that need the table then refuse.
 static uint8_t* upload(int device, const void* src, size_t bytes) {
@@ -2234,12 +2024,12 @@ static int reachability(const oc_handle* h, int32_t* num_nodes, uint16_t* node_o
     return OC_OK;
 }
 
-// Wide levels: n steps of the scalar kernel (oc_step: n = 1), statistics folded by
+// Wide levels: n steps of oc_step_wide_kernel (oc_step: n = 1), statistics folded by
 // oc_stats_reduce when totals are asked for.
 static int step_wide(const oc_handle* h, const void* sin, void* sout, const uint8_t* act, void* traj, uint8_t* ex,
                      uint8_t* coll, uint64_t* stats, uint64_t* totals, int64_t B, int32_t n, void* stream) {
     if (h->wide_tiles == nullptr) return fail(OC_EHIP, "level tables not on the device");
-    const WideArgs R = wide_args(h, B, (h->level.width * h->level.height + 3) / 4);
+    const WideArgs R{h->args.sw, (h->level.width * h->level.height + 3) / 4, pitch_for(B), B};
     // one lane per 4 envs; up to 8 blocks per CU (grid-stride past that)
     const int64_t need = ((B + kEPL - 1) / kEPL + kBlock - 1) / kBlock, cap = (int64_t)h->cus * 8;
     const dim3 grid((unsigned)(need < cap ? need : cap));
@@ -2419,18 +2209,16 @@ int oc_create(const oc_level_desc* lv, int32_t num_agents, int32_t max_T, int32_
     if (max_T < 0 || max_T > 65535) return fail(OC_EINVAL, "max_T %d", max_T);
     if (device < OC_DEVICE_HOST) return fail(OC_EINVAL, "device %d", device);
     const bool host_only = device == OC_DEVICE_HOST;  // no HIP call at all
-    const bool wide = W * H > ocro::kMaxCells;  // u16 cell ids: the scalar step (oc_step_wide_kernel)
+    const bool wide = W * H > ocro::kMaxCells;  // u16 cell ids: step4w (oc_step_wide_kernel)
     LevelArgs L{};
-    L.W = W;
-    L.H = H;
-    L.done_cell = -1;
+    int done_cell = -1;
     for (int c = 0; c < W * H; ++c) {
         const int t = lv->tiles[c];
         if (t < OC_TILE_FLOOR || t > OC_TILE_DELIVERY) return fail(OC_ELEVEL, "tile %d at cell %d", t, c);
         if (!wide) L.cls4[c >> 2] |= (uint32_t)ocsw::tile_class(t) << (8 * (c & 3));
-        if (t == OC_TILE_DELIVERY && L.done_cell < 0) L.done_cell = c;
+        if (t == OC_TILE_DELIVERY && done_cell < 0) done_cell = c;
     }
-    if (L.done_cell < 0) return fail(OC_ELEVEL, "no Delivery tile");
+    if (done_cell < 0) return fail(OC_ELEVEL, "no Delivery tile");
     if (lv->encoding != OC_ENC_PRESENCE && lv->encoding != OC_ENC_COUNTS)
         return fail(OC_EINVAL, "encoding %d", lv->encoding);
     const bool counts = lv->encoding == OC_ENC_COUNTS;
@@ -2466,23 +2254,12 @@ int oc_create(const oc_level_desc* lv, int32_t num_agents, int32_t max_T, int32_
     for (int a = 0; a < num_agents; ++a) {
         const int x = lv->spawn_x[a], y = lv->spawn_y[a];
         if (x >= W || y >= H || lv->tiles[y * W + x] != OC_TILE_FLOOR) return fail(OC_ELEVEL, "spawn %d not on Floor", a);
-        L.tmpl_x |= (uint32_t)x << (8 * a);
-        L.tmpl_y |= (uint32_t)y << (8 * a);
     }
-    for (int j = 0; j < 16; ++j) {
-        L.tmpl_cell[j >> 2] |= (uint32_t)cell8[j] << (8 * (j & 3));
-        L.tmpl_mask[j >> 2] |= (uint32_t)mask[j] << (8 * (j & 3));
-    }
-    for (int g = 0; g < lv->num_goals; ++g) L.goals |= (uint32_t)lv->goal_mask[g] << (8 * g);
-    L.ngoals = lv->num_goals;
-    L.max_T = max_T;
-    const int dcell[5] = {W, -W, -1, 1, 0};
-    for (int c = 0; c < 5; ++c) L.dcell_lut |= (uint64_t)((dcell[c] + 128) & 0xFF) << (8 * c);
-    ocsw::build_swar_level(L.sw, W, H, L.done_cell, lv->goal_mask, lv->num_goals, max_T, lv->spawn_x, lv->spawn_y,
+    ocsw::build_swar_level(L.sw, W, H, done_cell, lv->goal_mask, lv->num_goals, max_T, lv->spawn_x, lv->spawn_y,
                            num_agents, cell8, mask, lv->encoding, lv->tiles);
     if (wide) {  // step4w: u16 cells as low / high byte words (the LUTs, x / y and W - 1 stay bytes)
-        L.sw.done_rep = (uint32_t)(L.done_cell & 0xFF) * 0x01010101u;
-        L.sw.done_hi_rep = (uint32_t)(L.done_cell >> 8) * 0x01010101u;
+        L.sw.done_rep = (uint32_t)(done_cell & 0xFF) * 0x01010101u;
+        L.sw.done_hi_rep = (uint32_t)(done_cell >> 8) * 0x01010101u;
         for (int j = 0; j < 16; ++j) {
             L.sw.tmpl_l[j] = (uint32_t)(cell[j] & 0xFF) * 0x01010101u;
             L.sw.tmpl_lh[j] = (uint32_t)(cell[j] >> 8) * 0x01010101u;
@@ -2490,25 +2267,6 @@ int oc_create(const oc_level_desc* lv, int32_t num_agents, int32_t max_T, int32_
     }
     oc_handle* h = new oc_handle;
     h->wide = wide;
-    h->step = ocro::StepLevel{};
-    h->step.done_cell = L.done_cell;
-    h->step.max_T = max_T;
-    h->step.ngoals = lv->num_goals;
-    for (int g = 0; g < lv->num_goals; ++g) h->step.goal[g] = lv->goal_mask[g];
-    for (int a = 0; a < num_agents; ++a) {
-        h->step.spawn_x[a] = lv->spawn_x[a];
-        h->step.spawn_y[a] = lv->spawn_y[a];
-    }
-    for (int j = 0; j < 16; ++j) {
-        h->step.item_cell[j] = cell[j];
-        h->step.item_mask[j] = mask[j];
-    }
-    h->step_lv = ocro::RollLevel{};
-    h->step_lv.W = W;
-    h->step_lv.H = H;
-    h->step_lv.perimeter = 2 * (W + H);
-    h->step_lv.enc = lv->encoding;
-    h->step_lv.wide = wide ? 1 : 0;
     memset(h->wide_tiles_host, 0, sizeof h->wide_tiles_host);
     for (int c = 0; c < W * H; ++c) h->wide_tiles_host[c] = lv->tiles[c];
     h->level = *lv;
@@ -2607,21 +2365,11 @@ int oc_reset(const oc_handle* h, void* state, int64_t B, void* stream) {
     OC_NEED_DEVICE(h);
     if (B == 0) return OC_OK;
     hipStream_t s = (hipStream_t)stream;
-    if (h->wide) {
-        const WideArgs R = wide_args(h, B, 0);
-        const dim3 grid((unsigned)(R.pitch / kBlock));
-        return dispatch_ak(h->A, h->K, [&](auto a, auto k) {
-            hipLaunchKernelGGL((oc_reset_wide_kernel<a(), k()>), grid, dim3(kBlock), 0, s, R, (uint8_t*)state);
-            return hip_check("oc_reset (wide) launch");
-        });
-    }
-    LevelArgs L = h->args;
-    L.pitch = pitch_for(B);
-    L.B = B;
-    const dim3 grid((unsigned)(L.pitch / kEnvsPerBlock));
-    return dispatch_ak(h->A, h->K, [&](auto a, auto k) {
-        hipLaunchKernelGGL((oc_reset_kernel<a(), k()>), grid, dim3(kBlock), 0, s, L, (uint8_t*)state);
-        return hip_check("oc_reset launch");
+    const int64_t P = pitch_for(B);
+    const dim3 grid((unsigned)(P / kEnvsPerBlock));
+    return dispatch_w(h, [&](auto a, auto k, auto w) {
+        hipLaunchKernelGGL((oc_reset_kernel<a(), k(), w()>), grid, dim3(kBlock), 0, s, h->args.sw, P, (uint8_t*)state);
+        return hip_check(h->wide ? "oc_reset (wide) launch" : "oc_reset launch");
     });
 }
 
@@ -2665,13 +2413,19 @@ int oc_cpu_step(const oc_handle* h, const void* state_in, void* state_out, const
         const uint8_t* si = (const uint8_t*)state_in;
         uint8_t* so = (uint8_t*)state_out;
         uint64_t* st = part.data() + i * OC_NSTATS;
-        if (h->wide)  // the wide SWAR step (step4w), four envs per word as the kernel
+        const ocsw::SwarLevel& sw = h->args.sw;
+        if (h->wide) {  // the wide SWAR step (step4w), four envs per word as the kernel
+            uint8_t cls[ocro::kMaxCellsWide];
+            for (int c = 0; c < ocro::kMaxCellsWide; ++c) cls[c] = ocsw::tile_class(h->wide_tiles_host[c]);
             return dispatch_ak(h->A, h->K, [&](auto a, auto k) {
-                cpu_step_wide<a(), k()>(h, si, so, actions, exec_actions, coll_mask, B, P, g0, g1, st);
+                ocio::host_step_range<1, a(), k(), true>(sw, WideClass{cls}, si, so, actions, exec_actions, coll_mask, B,
+                                                         P, g0, g1, st);
                 return OC_OK;
             });
+        }
         return dispatch_step(h, [&](auto a, auto k, auto mode) {
-            cpu_step_words<a(), k(), mode()>(h, si, so, actions, exec_actions, coll_mask, B, P, g0, g1, st);
+            ocio::host_step_range<mode(), a(), k(), false>(sw, NarrowClass{(const uint8_t*)h->args.cls4}, si, so, actions,
+                                                           exec_actions, coll_mask, B, P, g0, g1, st);
             return OC_OK;
         });
     });

@@ -116,17 +116,6 @@ struct RollLevel {  // scalars (kernel argument); the tables are in the blob
     int32_t pair_off;    // blob offset of the agent-pair table (device memory only), 0 = none
 };
 
-// A wide level's reset template (oc_reset_wide_kernel).
-struct StepLevel {
-    int32_t done_cell;  // first Delivery in scan order (done() reads only it, overcooked_environment.py:349)
-    int32_t max_T;      // 0 = no limit
-    int32_t ngoals;
-    uint8_t goal[4];    // Deliver goal masks
-    uint8_t spawn_x[4], spawn_y[4];
-    uint16_t item_cell[16];  // the template's item slots (dead past the level's items)
-    uint8_t item_mask[16];
-};
-
 struct Sub {  // oc_subtask, device copy
     int32_t kind, n;
     uint8_t agent[2], start[2], goal, count, level, pad;

@@ -5,7 +5,8 @@ instantiation reads or writes the wrong planes, so per cell:
 
   * oc_get_layout against the layout formula written out here;
   * oc_cpu_step against the CPU oracle over random play (states, executed actions, collision
-    masks, totals), with max_T = 5 so that episodes time out and auto-reset inside the 12 steps;
+    masks, totals), with max_T = 5 so that episodes time out and auto-reset inside the 12 steps,
+    and the columns the batch's last word may and may not write;
   * oc_cpu_observe against tests/obs_ref.py and oc_cpu_progress against tests/progress_ref.py on
     the states of that play.
 
@@ -125,6 +126,25 @@ def test_cpu_step_matches_oracle(A, K, shape):
         assert np.array_equal(coll[:B], ref.coll[t]), t
     assert np.array_equal(tot.astype(np.int64), ref.totals), (tot, ref.totals)
     assert ref.totals[0] >= 2 * B  # every env timed out and was reset, twice
+
+
+@pytest.mark.parametrize("A,K,shape", CELLS)
+def test_cpu_step_last_word_columns(A, K, shape):
+    """One oc_cpu_step into buffers prefilled with 0xA5: columns 0..6 are the oracle's, and a wide
+    level leaves column 7 of every plane (and env 7's two T bytes) as they were."""
+    ref = oracle_play(A, K, shape)
+    cs = CpuStepper(ref.level, A, B, MAX_T, nthreads=1)
+    P, NP = cs.pitch, cs.layout.num_planes
+    out, ex, coll = (np.full(n, 0xA5, np.uint8) for n in (NP * P, A * P, P))
+    cs.step(ref.s0.copy(), out, ref.acts[0], ex, coll)
+    assert np.array_equal(tl.env_view(out, A, K, P, B), tl.env_view(ref.states[0], A, K, P, B))
+    assert np.array_equal(ex.reshape(A, P)[:, :B], ref.ex[0]) and np.array_equal(coll[:B], ref.coll[0])
+    if shape == "wide":
+        planes, pt = out.reshape(NP, P), cs.layout.plane_t
+        byte_planes = [p for p in range(NP) if p not in (pt, pt + 1)]
+        assert (planes[byte_planes, B] == 0xA5).all()
+        assert (out[pt * P + 2 * B:pt * P + 2 * B + 2] == 0xA5).all()
+        assert (ex.reshape(A, P)[:, B] == 0xA5).all() and coll[B] == 0xA5
 
 
 @pytest.mark.parametrize("A,K,shape", CELLS)

@@ -1,9 +1,10 @@
 """Every cell of the engine's (A, K, narrow / wide) dispatch grid on the GPU: the 24 cells and
 levels of tests/test_dispatch_grid.py at B = 7, each kernel entry point against its host twin on
 the same bytes.  Per cell: oc_reset against the host template; six oc_step launches, and the same
-six steps as one oc_step_n launch with a trajectory, against oc_cpu_step; oc_state_checksum against
-its numpy twin; oc_observe (u8 and f16, with masks) against oc_cpu_observe; oc_progress against
-oc_cpu_progress."""
+six steps as one oc_step_n launch with a trajectory, as one without executed-action and collision
+buffers whose state_out is the trajectory's last slot and as one without a trajectory, against
+oc_cpu_step; oc_state_checksum against its numpy twin; oc_observe (u8 and f16, with masks) against
+oc_cpu_observe; oc_progress against oc_cpu_progress."""
 import numpy as np
 import pytest
 
@@ -75,6 +76,22 @@ def test_cell_kernels_match_host(A, K, shape):
     assert np.array_equal(exn.cpu().numpy().reshape(N, A, P)[:, :, :B], np.stack(want_ex))
     assert np.array_equal(colln.cpu().numpy().reshape(N, P)[:, :B], np.stack(want_coll))
     assert np.array_equal(totals.cpu().numpy(), want_tot)
+
+    # absent outputs: no executed-action and no collision buffer, state_out the trajectory's last slot
+    # (the launch writes it once, as that slot); then no trajectory at all.  This pins the zero-record
+    # descriptors of each layout's own kernel (oc_step_n_kernel, oc_step_wide_kernel)
+    traj2 = torch.empty(N * nb, dtype=torch.uint8, device=DEV)
+    tot2 = torch.zeros(capi.OC_NSTATS, dtype=torch.int64, device=DEV)
+    eb.step_n(s0, traj2[(N - 1) * nb:], dacts.reshape(-1), N, traj2, None, None, eb.new_stats(), tot2)
+    ht2 = traj2.cpu().numpy()
+    for t in range(N):
+        assert np.array_equal(view(ht2[t * nb:(t + 1) * nb]), view(want_s[t])), t
+    assert np.array_equal(tot2.cpu().numpy(), want_tot)
+    out3 = eb.new_state()
+    tot3 = torch.zeros(capi.OC_NSTATS, dtype=torch.int64, device=DEV)
+    eb.step_n(s0, out3, dacts.reshape(-1), N, None, None, None, eb.new_stats(), tot3)
+    assert np.array_equal(view(out3.cpu().numpy()), view(want_s[-1]))
+    assert np.array_equal(tot3.cpu().numpy(), want_tot)
 
     got = int(eb.checksum(out).cpu().numpy().view(np.uint64)[0])
     assert got == tl.checksum(want_s[-1], A, K, P, B)

@@ -1,11 +1,11 @@
 """Kitchens of more than 255 cells (user levels past the byte cell ids) on the
 CPU: the engine's wide layout (u16 item cells, include/oc_engine.h oc_layout.cell_bytes) and
-its scalar step (oc_rollout.h RowOps::env_step), pinned to the reference's own runs of the same
-level files (tests/golden/gen_widelevels.py: a 17x17 Salad kitchen of 289 cells, a 23x13
+its SWAR step (oc_swar.h step4w: cells as low / high byte words), pinned to the reference's own
+runs of the same level files (tests/golden/gen_widelevels.py: a 17x17 Salad kitchen of 289 cells, a 23x13
 two-recipe kitchen of 299 cells with 5 items and two Delivery squares):
 
 * the parser against load_level / reset's tables and the reachability graph's node count;
-* the CPU oracle and oc_cpu_step (the product library's host pass of the scalar step) against
+* the CPU oracle and oc_cpu_step (the product library's host pass of that step) against
   every recorded episode (1-4 agents, uniform and goal-directed);
 * oc_cpu_step against the oracle in random play (timeouts, auto-resets, ERR ends, collisions),
   with the window statistics;

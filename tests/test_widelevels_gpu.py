@@ -1,6 +1,6 @@
 """Kitchens of more than 255 cells on the GPU, through the C-ABI (the wide layout: u16 item
 cells; fixtures from tests/golden/gen_widelevels.py, which runs the reference on the same level
-files).  oc_step replays the recorded episodes; oc_step_n (the scalar wide kernel) against the
+files).  oc_step replays the recorded episodes; oc_step_n (oc_step_wide_kernel: the SWAR step4w) against the
 CPU oracle on every step's outputs, the in-launch totals and the checksum; oc_reset against the
 template; oc_subtask_bounds and oc_rollout against the reference's rows; rollout, bounds and
 likelihood rows against the oracle on random states; the gym shim replays the episodes; the

@@ -106,7 +106,7 @@ __global__ __launch_bounds__(SW * 64 + (LW ? 64 : 0), LW ? LB : 1) void stepn_tl
         __builtin_amdgcn_s_waitcnt(0x0F70);
         if (rec) out[1] = now();
         const uint32_t vo = g * 4u;
-        uint32_t T0 = c.wt.x, T1 = c.wt.y;
+        uint32_t T0 = c.t0, T1 = c.t1;
         uint32_t pending = ocsw::at_done80<K, MODE>(L.sw, c.wl);
         const int64_t rem = L.B - (int64_t)g * kEPL;
         const uint32_t vmask = rem >= kEPL ? 0xFFFFFFFFu : (rem <= 0 ? 0u : (1u << (8 * (uint32_t)rem)) - 1u);
@@ -293,11 +293,12 @@ __global__ __launch_bounds__(5 * 64, 5) void stepn_seg(LevelArgs L, const uint8_
                 ch.wm[j] = bld32<kCPsc1>(rs, vo, base + (kPM + j) * P);
             }
             const auto t = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)(g * 8u), (int)(base + kPT * P), kCPsc1);
-            ch.wt = make_uint2(t[0], t[1]);
+            ch.t0 = t[0];
+            ch.t1 = t[1];
             ch.wf = bld32<kCPsc1>(rs, vo, base + kPF * P);
         }
         __builtin_amdgcn_s_waitcnt(0x0F70);
-        uint32_t T0 = ch.wt.x, T1 = ch.wt.y;
+        uint32_t T0 = ch.t0, T1 = ch.t1;
         uint32_t pending = ocsw::at_done80<K, MODE>(L.sw, ch.wl);
         const int64_t rem = L.B - (int64_t)g * kEPL;
         const uint32_t vmask = rem >= kEPL ? 0xFFFFFFFFu : (rem <= 0 ? 0u : (1u << (8 * (uint32_t)rem)) - 1u);

@@ -16,8 +16,9 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# the last one is a wide level (576 cells, u16 cell ids: oc_step_wide_kernel), bench.py's `wide` shape
 CONFIGS = [("partial-divider_salad", 2, 20), ("partial-divider_salad", 2, 100), ("full-divider_tl", 3, 100),
-           ("full-divider_salad", 4, 100)]
+           ("full-divider_salad", 4, 100), ("tests/golden/levels/widegraph-24x24_salad.txt", 2, 20)]
 PER_STEP_CONFIGS = [("partial-divider_salad", 2, 20), ("full-divider_tl", 3, 20)]
 
 
@@ -27,7 +28,8 @@ def child(lib, level, A, n, B, reps):
     from gym_cooking_amd import capi
     capi.load_library(lib)
     from gym_cooking_amd.engine import OvercookedBatch
-    eb = OvercookedBatch(level, A, B, max_T=100, device="cuda:0")
+    eb = OvercookedBatch(os.path.join(ROOT, level) if level.endswith(".txt") else level, A, B, max_T=100,
+                         device="cuda:0")
     P, S = eb.pitch, eb.layout.state_bytes
     acts = torch.empty((n, A * P), dtype=torch.uint8, device="cuda:0")
     for i in range(n):

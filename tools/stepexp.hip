@@ -59,7 +59,7 @@ __global__ __launch_bounds__(BS) void step_flat(LevelArgs L, const uint8_t* __re
                 bst32<CP>(b.sout, c[i].wm[j], vo, (kPM + j) * P);
             }
             typedef unsigned int u32x2 __attribute__((__vector_size__(2 * sizeof(unsigned int))));
-            const u32x2 tw = {c[i].wt.x, c[i].wt.y};
+            const u32x2 tw = {c[i].t0, c[i].t1};
             __builtin_amdgcn_raw_buffer_store_b64(tw, b.sout, (int)((g0 + i * span) * 8u), (int)(kPT * P), CP);
             bst32<CP>(b.sout, c[i].wf, vo, kPF * P);
             bst32<CP>(b.coll, c[i].wf, vo, 0u);
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(BS) void step_timeline(LevelArgs L, const uint8_t* 
             bst32<CP>(b.sout, c.wm[j], vo, (kPM + j) * P);
         }
         typedef unsigned int u32x2 __attribute__((__vector_size__(2 * sizeof(unsigned int))));
-        const u32x2 tw = {c.wt.x, c.wt.y};
+        const u32x2 tw = {c.t0, c.t1};
         __builtin_amdgcn_raw_buffer_store_b64(tw, b.sout, (int)(g * 8u), (int)(kPT * P), CP);
         bst32<CP>(b.sout, c.wf, vo, kPF * P);
         bst32<CP>(b.coll, c.wf, vo, 0u);
