@@ -19,6 +19,7 @@
 //   oc_render_kernel  image observations.
 //   oc_observe_kernel grid feature planes + legal-move masks per env (oc_observe.h).
 //   oc_progress_kernel per-subtask object counts, completion events, shaped reward (oc_progress.h).
+//   oc_reset_random_kernel randomised episode starts, all envs or the DONE ones (oc_startdist.h).
 //   reset / gen_actions / checksum / stats_reduce helpers.
 // All of them accumulate nothing on the host; statistics are per-block rows of no-return
 // 64-bit atomics reduced by oc_stats_reduce for the all-gather of episode summaries.
@@ -39,6 +40,7 @@
 #include "oc_observe.h"
 #include "oc_progress.h"
 #include "oc_rollout.h"
+#include "oc_startdist.h"
 #include "oc_stepio.h"
 #include "oc_swar.h"
 
@@ -1681,6 +1683,14 @@ __global__ __launch_bounds__(kBlock) void oc_render_kernel(RenderArgs R, const u
 struct GlobalWords {
     uint8_t* s;
     int64_t P, g;
+    __device__ __forceinline__ uint32_t ld32(int plane) const {
+        return *reinterpret_cast<const uint32_t*>(s + plane * P + 4 * g);
+    }
+    __device__ __forceinline__ void ld64(int plane, uint32_t& lo, uint32_t& hi) const {
+        const uint2 v = *reinterpret_cast<const uint2*>(s + plane * P + 8 * g);
+        lo = v.x;
+        hi = v.y;
+    }
     __device__ __forceinline__ void st32(int plane, uint32_t v) const {
         *reinterpret_cast<uint32_t*>(s + plane * P + 4 * g) = v;
     }
@@ -1691,6 +1701,68 @@ struct GlobalWords {
 template <int A, int K, bool WIDE>
 __global__ __launch_bounds__(kBlock) void oc_reset_kernel(ocsw::SwarLevel sw, int64_t pitch, uint8_t* __restrict__ s) {
     ocio::store(ocio::template_chunk<A, K, WIDE>(sw), GlobalWords{s, pitch, (int64_t)blockIdx.x * kBlock + threadIdx.x});
+}
+
+// Randomised starts (oc_startdist.h), one lane per 4-env word as the step.  The handle's lists, the
+// x / y table and the agent_ok bytes are staged in LDS once per block ((A + 2) lists of u16 and A
+// byte tables: 3.5 KiB at most on a narrow level, 16 KiB on a wide one with four agents).  Full mode
+// (sprev null): every lane below B stores its whole chunk, the batch's last word completed with the
+// template.  Masked mode: the lane's flags word of sprev is loaded first; a block without a DONE env
+// leaves before the staging, a wave without one after it behind a wave-uniform test, a lane without
+// one stores nothing, and a lane with some loads its chunk of `s`, merges the restarting envs' bytes
+// into it and stores the words back (a lane owns its words; s may be sprev).  The masked call follows
+// every step, so its critical path is kept short: the table words are fetched into registers together
+// with the flags word (one memory round trip before the block's decision, not two), the chunk of `s`
+// is requested before the draws and arrives while they run, and the draws take every lane's lowest
+// restarting env per round (ocsd::start_chunk).
+template <int A, int K, bool WIDE>
+__global__ __launch_bounds__(ocsd::kBlock) void oc_reset_random_kernel(ocsw::SwarLevel sw, ocsd::StartArgs R,
+                                                                       const uint32_t* __restrict__ tab_g,
+                                                                       int tab_words, uint8_t* s,
+                                                                       const uint8_t* sprev) {
+    constexpr int NC = WIDE ? OC_MAX_CELLS : 256;
+    constexpr int kWords = ((A + 2) * NC * 2 + A * NC) / 4, kPre = (kWords + ocsd::kBlock - 1) / ocsd::kBlock;
+    __shared__ uint32_t tab[kWords];
+    uint32_t pre[kPre];
+#pragma unroll
+    for (int i = 0; i < kPre; ++i) {
+        const int w = i * ocsd::kBlock + (int)threadIdx.x;
+        pre[i] = w < tab_words ? tab_g[w] : 0u;
+    }
+    const int64_t g = (int64_t)blockIdx.x * ocsd::kBlock + threadIdx.x;
+    const int64_t rem = R.B - 4 * g;
+    const uint32_t vmask = ocio::valid_mask(R.B, g);
+    uint32_t done = 0u;  // 0x01 per restarting env (masked mode)
+    if (R.masked) {
+        if (rem > 0) done = *reinterpret_cast<const uint32_t*>(sprev + Planes<A, K, WIDE>::F * R.pitch + 4 * g);
+        done &= vmask & ocsw::k01 * OC_FLAG_DONE;
+        if (!__syncthreads_or(done != 0u)) return;
+    }
+#pragma unroll
+    for (int i = 0; i < kPre; ++i) {
+        const int w = i * ocsd::kBlock + (int)threadIdx.x;
+        if (w < tab_words) tab[w] = pre[i];
+    }
+    __syncthreads();
+    if (rem <= 0) return;
+    uint32_t sel;
+    if (R.masked) {
+        if (__ballot(done != 0u) == 0ull) return;
+        if (done == 0u) return;
+        sel = (done & 1u) | ((done >> 7) & 2u) | ((done >> 14) & 4u) | ((done >> 21) & 8u);
+    } else {
+        sel = rem >= 4 ? 0xFu : (1u << (uint32_t)rem) - 1u;
+    }
+    const GlobalWords out{s, R.pitch, g};
+    Chunk<A, K, WIDE> c, o;
+    if (R.masked) ocio::load<false>(o, out, out);
+    ocsd::start_chunk<A, K, WIDE>(sw, R, ocsd::tab_of<A>(tab, R), g, sel, c);
+    if (R.masked) {
+        ocsd::merge(o, c, (done << 8) - done);  // 0x01 -> 0xFF per byte
+        ocio::store(o, out);
+    } else {
+        ocio::store(c, out);
+    }
 }
 
 // Order-sensitive 64-bit checksum of the state of envs [0, B):
@@ -1819,6 +1891,14 @@ struct oc_handle {
     int32_t obs_static_off = 0, obs_nstatic = 0;
     int32_t obs_nt = 0;              // non-temporal output stores (OC_OBS_STORES=nt|plain overrides)
     int32_t obs_tile = ocob::kMaxTileEnvs;  // envs per block at most (OC_OBS_TILE=64|32|16|... overrides)
+    // oc_reset_random: the start distribution (oc_startdist.h).  start_ok: agent_ok [A][W*H] then
+    // item_ok [W*H], the effective masks; start_tab_host / start_tab: the table blob and its device
+    // copy; start_err: why there is no valid distribution (the defaults are too short for the level)
+    std::vector<uint8_t> start_ok, start_tab_host;
+    uint8_t* start_tab = nullptr;
+    ocsd::StartArgs start{};
+    int start_rc = OC_OK;
+    std::string start_err;
     mutable std::string last_error;       // oc_get_last_error: the last failed call on this handle
 };
 
@@ -2172,6 +2252,108 @@ static int progress_args(const oc_handle* h, const void* state_prev, const void*
     return OC_OK;
 }
 
+// The start distribution of oc_set_start_cells(h, agent_ok, item_ok) (NULL: the default lists of
+// include/oc_engine.h): checks it and builds the effective masks, the list lengths and the table
+// blob (ocsd::table_bytes).  Returns OC_OK, or the code with its message in `err`; the handle is not
+// touched.
+static int build_start(const oc_handle* h, const uint8_t* agent_ok, const uint8_t* item_ok, std::vector<uint8_t>& ok,
+                       std::vector<uint8_t>& tab, ocsd::StartArgs& R, std::string& err) {
+    const oc_level_desc& lv = h->level;
+    const int W = lv.width, H = lv.height, cells = W * H, A = h->A;
+    char msg[256];
+    auto refuse = [&](int code) {
+        err = msg;
+        return code;
+    };
+    ok.assign((size_t)(A + 1) * cells, 0);
+    for (int i = 0; i < A; ++i) {
+        uint8_t* m = ok.data() + (size_t)i * cells;
+        if (agent_ok != nullptr) {
+            for (int c = 0; c < cells; ++c) {
+                m[c] = agent_ok[(size_t)i * cells + c] != 0;
+                if (m[c] && lv.tiles[c] != OC_TILE_FLOOR) {
+                    snprintf(msg, sizeof msg, "start cells: agent %d cell %d (%d,%d) is not Floor", i, c, c % W, c / W);
+                    return refuse(OC_EINVAL);
+                }
+            }
+        } else {  // the Floor cells 4-connected through Floor to spawn i
+            std::vector<int> todo{lv.spawn_y[i] * W + lv.spawn_x[i]};
+            m[todo[0]] = 1;
+            while (!todo.empty()) {
+                const int c = todo.back(), x = c % W, y = c / W;
+                todo.pop_back();
+                const int nb[4] = {y + 1 < H ? c + W : -1, y > 0 ? c - W : -1, x > 0 ? c - 1 : -1, x + 1 < W ? c + 1 : -1};
+                for (int n : nb)
+                    if (n >= 0 && lv.tiles[n] == OC_TILE_FLOOR && !m[n]) {
+                        m[n] = 1;
+                        todo.push_back(n);
+                    }
+            }
+        }
+    }
+    uint8_t* mi = ok.data() + (size_t)A * cells;
+    for (int c = 0; c < cells; ++c) {
+        const int x = c % W, y = c / W;
+        if (item_ok != nullptr) {
+            mi[c] = item_ok[c] != 0;
+            if (mi[c] && lv.tiles[c] != OC_TILE_COUNTER) {
+                snprintf(msg, sizeof msg, "start cells: item cell %d (%d,%d) is not a Counter", c, x, y);
+                return refuse(OC_EINVAL);
+            }
+        } else {  // a Counter with a Floor 4-neighbour
+            const bool fl = (y + 1 < H && lv.tiles[c + W] == OC_TILE_FLOOR) || (y > 0 && lv.tiles[c - W] == OC_TILE_FLOOR) ||
+                            (x > 0 && lv.tiles[c - 1] == OC_TILE_FLOOR) || (x + 1 < W && lv.tiles[c + 1] == OC_TILE_FLOOR);
+            mi[c] = lv.tiles[c] == OC_TILE_COUNTER && fl;
+        }
+    }
+    R = ocsd::StartArgs{};
+    R.S = (cells + 1) & ~1;
+    R.S2 = (cells + 3) & ~3;
+    R.items = lv.num_items;
+    tab.assign((size_t)ocsd::table_bytes(A, R.S, R.S2), 0);
+    uint16_t* L = (uint16_t*)tab.data();
+    for (int i = 0; i <= A; ++i) {
+        int n = 0;
+        for (int c = 0; c < cells; ++c)
+            if (ok[(size_t)i * cells + c]) L[i * R.S + n++] = (uint16_t)c;
+        if (i < A) {
+            R.nA[i] = n;
+            if (n < A) {
+                snprintf(msg, sizeof msg, "start cells: agent %d has %d cells, fewer than the %d agents", i, n, A);
+                return refuse(agent_ok != nullptr ? OC_EINVAL : OC_ELEVEL);
+            }
+        } else {
+            R.nI = n;
+            if (n < lv.num_items) {
+                snprintf(msg, sizeof msg, "start cells: %d item cells, fewer than the level's %d items", n, lv.num_items);
+                return refuse(item_ok != nullptr ? OC_EINVAL : OC_ELEVEL);
+            }
+        }
+    }
+    for (int c = 0; c < cells; ++c) L[(A + 1) * R.S + c] = (uint16_t)((c % W) | ((c / W) << 8));
+    uint8_t* okb = tab.data() + (size_t)(A + 2) * R.S * 2;
+    for (int i = 0; i < A; ++i) memcpy(okb + (size_t)i * R.S2, ok.data() + (size_t)i * cells, (size_t)cells);
+    return OC_OK;
+}
+
+// oc_reset_random / oc_cpu_reset_random: the arguments both check, and the call's StartArgs
+static int start_args(const oc_handle* h, const void* state, int64_t B, int64_t env_offset, uint64_t seed, uint64_t round,
+                      int32_t what, bool masked, ocsd::StartArgs& R) {
+    if (state == nullptr || B < 0 || env_offset < 0) return fail(OC_EINVAL, "bad argument");
+    if (what == 0 || (what & ~(OC_START_AGENTS | OC_START_ITEMS)))
+        return fail(OC_EINVAL, "reset_random: what = %d (OC_START_AGENTS | OC_START_ITEMS, not 0)", what);
+    if (h->start_rc != OC_OK) return fail(h->start_rc, "%s", h->start_err.c_str());
+    R = h->start;
+    R.what = what;
+    R.masked = masked ? 1 : 0;
+    R.pitch = pitch_for(B);
+    R.B = B;
+    R.env_offset = env_offset;
+    R.seed = seed;
+    R.round = round;
+    return OC_OK;
+}
+
 extern "C" {
 
 int oc_abi_version(void) { return OC_ABI_VERSION; }
@@ -2316,6 +2498,11 @@ int oc_create(const oc_level_desc* lv, int32_t num_agents, int32_t max_T, int32_
         // null: oc_cpu_observe only
         if (!host_only) h->obs_tab = upload(device, h->obs_tab_host.data(), h->obs_tab_host.size());
     }
+    // oc_reset_random's default start distribution; a level it does not fit still loads, and the
+    // start calls refuse it with the message kept here
+    h->start_rc = build_start(h, nullptr, nullptr, h->start_ok, h->start_tab_host, h->start, h->start_err);
+    if (h->start_rc == OC_OK && !host_only)  // null: oc_cpu_reset_random only
+        h->start_tab = upload(device, h->start_tab_host.data(), h->start_tab_host.size());
     *out = h;
     return OC_OK;
 }
@@ -2334,6 +2521,7 @@ int oc_destroy(oc_handle* h) {
     if (h != nullptr && h->roll_blob != nullptr) (void)hipFree(h->roll_blob);
     if (h != nullptr && h->wide_tiles != nullptr) (void)hipFree(h->wide_tiles);
     if (h != nullptr && h->obs_tab != nullptr) (void)hipFree(h->obs_tab);
+    if (h != nullptr && h->start_tab != nullptr) (void)hipFree(h->start_tab);
     delete h;
     return OC_OK;
 }
@@ -2753,6 +2941,72 @@ int oc_cpu_progress(const oc_handle* h, const void* state_prev, const void* stat
         return dispatch_w(h, [&](auto a, auto k, auto w) {
             ocpg::cpu_progress_words<a(), k(), w()>(R, tab, (const uint8_t*)state_prev, (const uint8_t*)states, counts,
                                                     events, reward, g0, g1);
+            return OC_OK;
+        });
+    });
+}
+
+int oc_set_start_cells(oc_handle* h, const uint8_t* agent_ok, const uint8_t* item_ok) {
+    if (h == nullptr) return fail(OC_EINVAL, "bad argument");
+    ErrScope es_(h);
+    std::vector<uint8_t> ok, tab;
+    ocsd::StartArgs R;
+    std::string err;
+    if (const int rc = build_start(h, agent_ok, item_ok, ok, tab, R, err)) return fail(rc, "%s", err.c_str());
+    if (h->start_tab != nullptr) (void)hipFree(h->start_tab);  // waits for the device
+    h->start_tab = h->device >= 0 ? upload(h->device, tab.data(), tab.size()) : nullptr;
+    h->start_ok.swap(ok);
+    h->start_tab_host.swap(tab);
+    h->start = R;
+    h->start_rc = OC_OK;
+    h->start_err.clear();
+    return OC_OK;
+}
+
+int oc_get_start_cells(const oc_handle* h, uint8_t* agent_ok, uint8_t* item_ok) {
+    if (h == nullptr) return fail(OC_EINVAL, "bad argument");
+    ErrScope es_(h);
+    const size_t cells = (size_t)h->level.width * h->level.height, A = (size_t)h->A;
+    if (agent_ok != nullptr) memcpy(agent_ok, h->start_ok.data(), A * cells);
+    if (item_ok != nullptr) memcpy(item_ok, h->start_ok.data() + A * cells, cells);
+    return OC_OK;
+}
+
+int oc_reset_random(const oc_handle* h, void* state, const void* state_prev, int64_t B, int64_t env_offset,
+                    uint64_t seed, uint64_t round, int32_t what, void* stream) {
+    if (h == nullptr) return fail(OC_EINVAL, "bad argument");
+    ErrScope es_(h);
+    OC_NEED_DEVICE(h);
+    ocsd::StartArgs R;
+    if (const int rc = start_args(h, state, B, env_offset, seed, round, what, state_prev != nullptr, R)) return rc;
+    if (((uintptr_t)state | (uintptr_t)state_prev) & 7u) return fail(OC_EINVAL, "buffers must be 8-byte aligned");
+    if (h->start_tab == nullptr) return fail(OC_EHIP, "reset_random: the start table is not on the device");
+    if (B == 0) return OC_OK;
+    const int64_t lanes = (B + kEPL - 1) / kEPL;  // one lane per word of the batch
+    const dim3 grid((unsigned)((lanes + ocsd::kBlock - 1) / ocsd::kBlock));
+    const int tab_words = (int)(h->start_tab_host.size() / 4);
+    hipStream_t st = (hipStream_t)stream;
+    return dispatch_w(h, [&](auto a, auto k, auto w) {
+        hipLaunchKernelGGL((oc_reset_random_kernel<a(), k(), w()>), grid, dim3(ocsd::kBlock), 0, st, h->args.sw, R,
+                           (const uint32_t*)h->start_tab, tab_words, (uint8_t*)state, (const uint8_t*)state_prev);
+        return hip_check("oc_reset_random launch");
+    });
+}
+
+int oc_cpu_reset_random(const oc_handle* h, void* state, const void* state_prev, int64_t B, int64_t env_offset,
+                        uint64_t seed, uint64_t round, int32_t what, int32_t nthreads) {
+    if (h == nullptr || nthreads < 0) return fail(OC_EINVAL, "bad argument");
+    ErrScope es_(h);
+    ocsd::StartArgs R;
+    if (const int rc = start_args(h, state, B, env_offset, seed, round, what, state_prev != nullptr, R)) return rc;
+    if (B == 0) return OC_OK;
+    const int64_t words = (B + kEPL - 1) / kEPL;
+    const int64_t nt = host_threads(nthreads, words, 4096);  // >= 4096 words (16 Ki envs) per thread
+    return run_ranges(nt, [&](int64_t i) {
+        const int64_t g0 = words * i / nt, g1 = words * (i + 1) / nt;
+        return dispatch_w(h, [&](auto a, auto k, auto w) {
+            ocsd::host_start_range<a(), k(), w()>(h->args.sw, R, h->start_tab_host.data(), (uint8_t*)state,
+                                                  (const uint8_t*)state_prev, g0, g1);
             return OC_OK;
         });
     });

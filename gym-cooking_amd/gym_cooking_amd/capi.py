@@ -38,7 +38,11 @@ EXPORTED_SYMBOLS = (
     "oc_step", "oc_step_n", "oc_cpu_step", "oc_rollout", "oc_nav_likelihood", "oc_subtask_bounds", "oc_reachability", "oc_reachability16", "oc_render", "oc_render_ordered",
     "oc_gen_actions", "oc_state_checksum", "oc_stats_size", "oc_stats_reduce", "oc_get_last_error",
     "oc_set_likelihood_form", "oc_observe", "oc_cpu_observe", "oc_progress", "oc_cpu_progress",
+    "oc_set_start_cells", "oc_get_start_cells", "oc_reset_random", "oc_cpu_reset_random",
 )
+
+# oc_reset_random: which parts of a start are drawn (the rest keeps the level template)
+OC_START_AGENTS, OC_START_ITEMS = 1, 2
 
 
 # oc_observe: grid feature planes (3 static + 7 item + A agent channels) and legal-move masks
@@ -251,6 +255,14 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.oc_progress.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, i64, vp]
     lib.oc_cpu_progress.restype = ctypes.c_int
     lib.oc_cpu_progress.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, i64, i32]
+    lib.oc_set_start_cells.restype = ctypes.c_int
+    lib.oc_set_start_cells.argtypes = [vp, vp, vp]
+    lib.oc_get_start_cells.restype = ctypes.c_int
+    lib.oc_get_start_cells.argtypes = [vp, vp, vp]
+    lib.oc_reset_random.restype = ctypes.c_int
+    lib.oc_reset_random.argtypes = [vp, vp, vp, i64, i64, u64, u64, i32, vp]
+    lib.oc_cpu_reset_random.restype = ctypes.c_int
+    lib.oc_cpu_reset_random.argtypes = [vp, vp, vp, i64, i64, u64, u64, i32, i32]
     lib.oc_cpu_step.restype = ctypes.c_int
     lib.oc_cpu_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i32]
     lib.oc_step_n.restype = ctypes.c_int

@@ -36,7 +36,37 @@ def _bound(fn, args):
     return launch
 
 
-class OvercookedBatch:
+class _StartCells:
+    """oc_set_start_cells / oc_get_start_cells of a handle (OvercookedBatch and CpuStepper)."""
+
+    def set_start_cells(self, agent_ok=None, item_ok=None) -> None:
+        """The start distribution of reset_random: `agent_ok` [A, W*H] (non-zero: agent i may start
+        on the Floor cell) and `item_ok` [W*H] (non-zero: an item may start on the Counter cell);
+        None is the default (agent i: the Floor cells connected to spawn i; items: the Counters
+        with a Floor neighbour).  Not stream-ordered: earlier calls on the handle must have
+        completed.  A mask the engine refuses raises with its message."""
+        cells = self.level.width * self.level.height
+
+        def mask(m, n):
+            if m is None:
+                return None
+            m = np.ascontiguousarray(np.asarray(m) != 0, dtype=np.uint8).reshape(-1)
+            if m.size != n:
+                raise ValueError("start mask: %d cells, expected %d" % (m.size, n))
+            return m
+        a, i = mask(agent_ok, self.A * cells), mask(item_ok, cells)
+        capi.check(self.lib.oc_set_start_cells(self._h, None if a is None else a.ctypes.data,
+                                               None if i is None else i.ctypes.data))
+
+    def start_cells(self):
+        """The effective masks (agent_ok u8 [A, W*H], item_ok u8 [W*H]), defaults included."""
+        cells = self.level.width * self.level.height
+        a, i = np.zeros((self.A, cells), np.uint8), np.zeros(cells, np.uint8)
+        capi.check(self.lib.oc_get_start_cells(self._h, a.ctypes.data, i.ctypes.data))
+        return a, i
+
+
+class OvercookedBatch(_StartCells):
     """B envs of one level on one GPU.
 
     Args:
@@ -137,6 +167,28 @@ class OvercookedBatch:
         self._check(state, self.layout.state_bytes)
         capi.check(self.lib.oc_reset(self._h, _ptr(state), self.B, self._stream()))
         return state
+
+    def reset_random(self, state: torch.Tensor, prev: Optional[torch.Tensor] = None, seed: int = 0, round: int = 0,
+                     what: int = 3, env_offset: int = 0) -> torch.Tensor:
+        """Randomised starts (oc_reset_random): per env the agents on drawn Floor cells
+        (what & capi.OC_START_AGENTS) and the level's items on drawn Counter cells
+        (what & capi.OC_START_ITEMS), the reset of the level file with its item letters and spawn
+        lines moved there.  With `prev` only the envs whose `prev` flags carry DONE are rewritten
+        (after step(prev, state): exactly the envs the step auto-reset; `prev` may be `state`).
+        The draw depends on (seed, round, env_offset + env) only."""
+        self.reset_random_launcher(state, prev, seed, round, what, env_offset)()
+        return state
+
+    def reset_random_launcher(self, state: torch.Tensor, prev: Optional[torch.Tensor] = None, seed: int = 0,
+                              round: int = 0, what: int = 3, env_offset: int = 0):
+        """An oc_reset_random call bound once (see rollout_launcher)."""
+        self._check(state, self.layout.state_bytes)
+        if prev is not None:
+            self._check(prev, self.layout.state_bytes)
+        mask = (1 << 64) - 1
+        args = (self._h, _ptr(state), _ptr(prev), self.B, int(env_offset), int(seed) & mask, int(round) & mask,
+                int(what), self._stream())
+        return _bound(self.lib.oc_reset_random, args)
 
     def step(self, state_in: torch.Tensor, state_out: torch.Tensor, actions: torch.Tensor,
              exec_out: Optional[torch.Tensor] = None, coll: Optional[torch.Tensor] = None,
@@ -388,7 +440,7 @@ class OvercookedBatch:
             raise ValueError("buffer must be 16-byte aligned")
 
 
-class CpuStepper:
+class CpuStepper(_StartCells):
     """oc_cpu_step: the engine's step on the host, for a caller without a GPU (numpy buffers in
     the oc_step layout).  The same SWAR step as the kernels (its host pass); the GPU path never
     calls it.  `step` mirrors OvercookedBatch.step (overcooked_environment.py:255-306)."""
@@ -443,6 +495,20 @@ class CpuStepper:
         capi.check(self.lib.oc_cpu_step(self._h, p(state_in), p(state_out), p(actions), p(exec_out), p(coll),
                                         p(totals), self.B, self.nthreads))
         return state_out
+
+    def reset_random(self, state: np.ndarray, prev: Optional[np.ndarray] = None, seed: int = 0, round: int = 0,
+                     what: int = 3, env_offset: int = 0) -> np.ndarray:
+        """oc_cpu_reset_random: randomised starts in the host states; mirrors
+        OvercookedBatch.reset_random (with `prev`, only its DONE envs are rewritten).  Only columns
+        below B are written."""
+        for a in (state, prev):
+            if a is not None and (a.dtype != np.uint8 or not a.flags.c_contiguous or a.nbytes < self.layout.state_bytes):
+                raise ValueError("host buffers: contiguous uint8 of at least %d bytes" % self.layout.state_bytes)
+        mask = (1 << 64) - 1
+        capi.check(self.lib.oc_cpu_reset_random(self._h, state.ctypes.data, None if prev is None else prev.ctypes.data,
+                                                self.B, int(env_offset), int(seed) & mask, int(round) & mask,
+                                                int(what), self.nthreads))
+        return state
 
     def observe(self, state: np.ndarray, dtype=np.uint8, view_agent: int = -1, want_mask: bool = True):
         """oc_cpu_observe: the grid observation [B, C, H, W] (np.uint8 or np.float16) and, with

@@ -799,9 +799,17 @@ class OvercookedVecEnv:
     env (``RealAgent.def_subtask_completion``), the completion events of the step
     (``is_subtask_complete``; bit b of plane c is subtask 8c + b) and a shaped reward, the sum
     of ``weights`` over the events (oc_progress).  It is opt-in: ``step()`` does not compute it.
+
+    ``random_starts`` (``capi.OC_START_AGENTS | capi.OC_START_ITEMS``, default 0: the level's own
+    start everywhere, exactly as without the argument) randomises episode starts with ``seed``:
+    ``reset()`` draws every env's agents and / or item cells (oc_reset_random, the reset of the level
+    file with its item letters and spawn lines moved), and ``step()`` follows its launch with the
+    masked call that redraws exactly the envs the step auto-reset, at round = the number of
+    ``step()`` calls so far.  ``batch.set_start_cells`` narrows or widens the eligible cells.
     """
 
-    def __init__(self, level, num_agents: int, num_envs: int, max_num_timesteps: int = 100, device="cuda:0"):
+    def __init__(self, level, num_agents: int, num_envs: int, max_num_timesteps: int = 100, device="cuda:0",
+                 random_starts: int = 0, seed: int = 0):
         from .engine import OvercookedBatch
         self.batch = OvercookedBatch(level, num_agents, num_envs, max_T=max_num_timesteps, device=device)
         self.num_envs, self.A, self.P = num_envs, num_agents, self.batch.pitch
@@ -812,6 +820,8 @@ class OvercookedVecEnv:
         self.stats = self.batch.new_stats()
         self._fl = self.batch.layout.plane_flags
         self._stepped = False  # progress(): whether the other ping-pong buffer is the state before
+        self.random_starts, self.seed = int(random_starts), int(seed)
+        self._round = 0  # step() calls so far: the round of the next draw
 
     @property
     def state(self) -> torch.Tensor:
@@ -829,7 +839,9 @@ class OvercookedVecEnv:
         return self.batch.planes(self.state)
 
     def reset(self) -> torch.Tensor:
-        self.batch.reset(self.state)
+        self.batch.reset(self.state)  # the whole pitch: the columns past B hold the template, as always
+        if self.random_starts:
+            self.batch.reset_random(self.state, None, self.seed, self._round, self.random_starts)
         self._stepped = False
         return self.state
 
@@ -842,6 +854,9 @@ class OvercookedVecEnv:
             act = self._act
         src, dst = self._s[self._i], self._s[self._i ^ 1]
         self.batch.step(src, dst, act, self.ex, self.coll, self.stats)
+        self._round += 1
+        if self.random_starts:  # the envs this step auto-reset (DONE in src) get a drawn start
+            self.batch.reset_random(dst, src, self.seed, self._round, self.random_starts)
         self._i ^= 1
         self._stepped = True
         fl = dst.view(-1, P)[self._fl, :B]

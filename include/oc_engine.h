@@ -15,6 +15,9 @@
  *                               get_single_actions (gym_cooking/navigation_planner/utils.py:55-90) per agent
  *   oc_progress, oc_cpu_progress <- RealAgent.def_subtask_completion / is_subtask_complete
  *                               (gym_cooking/utils/agent.py:286-368) for every subtask of a recipe, per env
+ *   oc_reset_random, oc_cpu_reset_random, oc_set_start_cells, oc_get_start_cells
+ *                            <- load_level (:144-193) + reset (:201-250) of the level file with its item
+ *                               letters and spawn lines moved, per env
  *   oc_gen_actions           <- synthetic action streams (the reference env has no RNG)
  *   oc_stats_*               <- the per-episode bookkeeping main.py keeps in its metrics Bag
  *                               (gym_cooking/misc/metrics/metrics_bag.py:40-72), reduced per GPU
@@ -555,6 +558,82 @@ int oc_progress(const oc_handle* h, const void* state_prev, const void* states, 
 int oc_cpu_progress(const oc_handle* h, const void* state_prev, const void* states, int32_t n,
                     const oc_subtask* subtasks, int32_t num_subtasks, const float* weights,
                     uint8_t* counts, uint8_t* events, float* reward, int64_t B, int32_t nthreads);
+
+/* ---------------------------------------------------------------------------------------
+ * Randomised episode starts (additive to ABI 12): per env, the agents on other Floor squares and
+ * the level's items on other Counter squares.  The reference has no batch and no randomisation, so
+ * the surface is build-defined like auto-reset; a drawn start is exactly the state the reference
+ * builds when it loads the level file with its item letters and spawn lines moved to the drawn
+ * cells: load_level (gym_cooking/envs/overcooked_environment.py:144-193) makes one object per map
+ * letter on a Counter (:158-165) and one agent per spawn line (:186-193).
+ *
+ * The start distribution of a handle: per agent i a list LA_i of Floor cells and one list LI of
+ * item cells, both in ascending cell id.  Defaults, from the level:
+ *   LA_i : the Floor cells 4-connected through Floor to spawn i (a full divider keeps each agent
+ *          on its own side)
+ *   LI   : the cells of class OC_TILE_COUNTER (not Cutboard, not Delivery) with at least one
+ *          Floor 4-neighbour.  The template may keep an item on a counter outside LI: the
+ *          template is not a draw.
+ * The draw of env e, global id gid = env_offset + e (identical for any split of the envs over
+ * GPUs, as oc_gen_actions):
+ *   base    = seed ^ gid * 0x9E3779B97F4A7C15 ^ round * 0xC2B2AE3D27D4EB4F
+ *   u(d)    = splitmix64(base ^ (0x53540000 + d))        (oc_gen_actions' splitmix64; the offset
+ *                                                         keeps the two streams apart)
+ *   r(d, n) = (uint32)(((u(d) >> 32) * n) >> 32)
+ *   agents i = 0..A-1 : with m = the earlier agents standing on a cell of LA_i, agent i takes the
+ *             r(i, |LA_i| - m)-th cell of LA_i, ascending, that no earlier agent occupies;
+ *             hold = OC_HOLD_NONE
+ *   items, live template slots k ascending : with j = the earlier live slots, slot k takes the
+ *             r(16 + k, |LI| - j)-th cell of LI, ascending, not taken by an earlier slot, and
+ *             keeps the template's mask byte; dead slots stay dead
+ *   t = 0, flags = 0.  A part `what` does not select keeps the template's values.
+ * Every draw is exact and bounded: no rejection loop, no fallback.
+ * ------------------------------------------------------------------------------------- */
+#define OC_START_AGENTS 1
+#define OC_START_ITEMS 2
+
+/* Set the handle's start distribution (what a caller of load_level chooses by editing the level
+ * file, overcooked_environment.py:144-193):
+ *   agent_ok : u8 [A][W*H], non-zero = agent i may start on the cell; NULL = the default lists
+ *   item_ok  : u8 [W*H], non-zero = an item may start on the cell; NULL = the default list
+ * Refused with a message, the handle unchanged: a non-Floor cell in agent_ok or a cell in item_ok
+ * that is not class Counter (OC_EINVAL), fewer than A cells in an agent's list or fewer item cells
+ * than the level has items (OC_EINVAL; OC_ELEVEL when it is the level's default list that is too
+ * short).  Host masks; may allocate and copy as oc_create does, is not stream-ordered (calls in
+ * flight on the handle must have completed), and works on OC_DEVICE_HOST handles. */
+int oc_set_start_cells(oc_handle* h, const uint8_t* agent_ok, const uint8_t* item_ok);
+
+/* The effective masks (defaults included) as 0 / 1 bytes: agent_ok u8 [A][W*H], item_ok u8 [W*H];
+ * either may be NULL. */
+int oc_get_start_cells(const oc_handle* h, uint8_t* agent_ok, uint8_t* item_ok);
+
+/* reset() (overcooked_environment.py:201-250) of the level file with moved letters and spawn lines,
+ * per env (the draw above).
+ *   state      : B states (oc_layout), device memory, 8-byte aligned
+ *   state_prev : NULL: every env below B gets a fresh start (reset()).  Else only the envs whose
+ *                state_prev flags carry OC_FLAG_DONE are written and every other byte of `state` is
+ *                left as it is: called after oc_step(state_prev -> state) it replaces exactly the
+ *                envs the step just auto-reset to the template (auto-reset's timing, t = 0 and
+ *                no-op executed actions, is unchanged).  state_prev == state restarts the DONE envs
+ *                in place (each word's flags are read before it is written).
+ *   env_offset : global id of env 0 (>= 0);  seed, round : the draw's;  what : OC_START_* bits
+ * Columns past B: with state_prev NULL the batch's last 4-env word may be completed with the
+ * template; nothing at or past the next multiple of 4 above B is written (unlike oc_reset, which
+ * fills the pitch: a buffer that has never been reset keeps whatever bytes it had in those columns,
+ * which the step kernels step but no output or statistic counts).  what = 0 or other bits,
+ * or a host-only handle, is OC_EINVAL; a level whose default lists are too short for it and that has
+ * no lists set is OC_ELEVEL.  Stream-ordered, no allocation, no synchronisation
+ * (hipGraph-capturable, as oc_step).  oc_step_n keeps template restarts inside a launch: its
+ * trajectories never hold a drawn start. */
+int oc_reset_random(const oc_handle* h, void* state, const void* state_prev, int64_t B, int64_t env_offset,
+                    uint64_t seed, uint64_t round, int32_t what, void* stream);
+
+/* The same on the host (what oc_cpu_step is to oc_step): HOST buffers, works on OC_DEVICE_HOST
+ * handles, the kernel's draw functions compiled for the host, threaded over word ranges (nthreads
+ * 0 = the host's hardware threads; at least 16 Ki envs each).  Nothing past column B is read or
+ * written.  It never touches the device; oc_reset_random never calls it. */
+int oc_cpu_reset_random(const oc_handle* h, void* state, const void* state_prev, int64_t B, int64_t env_offset,
+                        uint64_t seed, uint64_t round, int32_t what, int32_t nthreads);
 
 #ifdef __cplusplus
 }
