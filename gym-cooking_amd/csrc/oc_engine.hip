@@ -572,7 +572,7 @@ __device__ __forceinline__ void stage_roll_tables(const RollArgs& R, const uint8
 }
 
 template <int A, int K, bool W = false>
-__device__ __forceinline__ ocro::RowT<K, W> load_row(const uint8_t* __restrict__ sin, int64_t P, int64_t e) {
+__host__ __device__ __forceinline__ ocro::RowT<K, W> load_row(const uint8_t* __restrict__ sin, int64_t P, int64_t e) {
     using PL = Planes<A, K, W>;
     using Row = ocro::RowT<K, W>;
     Row r;
@@ -1021,6 +1021,128 @@ __global__ __launch_bounds__(kBlock) void oc_likelihood_kernel(RollArgs R, const
         }
         if (lane == 0) {
             out[e] = f == OC_LIK_OK ? v : 0.0;
+            out_flags[e] = (uint8_t)f;
+        }
+    }
+}
+
+// Subtask-following actions (oc_nav_policy): the generative side of the likelihood's agent model,
+// a sibling of oc_likelihood_kernel.  A group of G lanes per row, candidate k on lane k (G = 8
+// when every configuration has one agent: 5 candidates; G = 32 when one has two: 25): every lane
+// builds the row's Level-0 view, tests its candidate's legality and evaluates Q(s, k) with one
+// rollout when it is legal.  The group takes the min of Q (a butterfly: order-free), w_k =
+// exp(beta * (min - Q_k)) per lane, the sum of w in ascending k (every lane adds the group's
+// terms in that order: the sequential sum bit for bit) and p_k = w_k / S.  The draw walks the
+// p_k in ascending k as shuffles (every lane the same running sum); greedy is the lowest lane
+// whose Q is the min.  The None subtask's closed form is evaluated by every lane (four legality
+// tests, no rollout).  Lane k stores plane k of probs; the group's first lane stores the flags
+// and the subtask agents' action bytes (byte stores: the other agents' bytes stay).
+struct PolicyArgs {
+    double beta, nap;
+    int64_t env_offset, step;
+    uint64_t seed;
+    int32_t mode, num_cand;
+};
+template <int A, int K, int G, bool W, bool GD>
+__global__ __launch_bounds__(kBlock) void oc_policy_kernel(RollArgs R, PolicyArgs Q, const uint8_t* __restrict__ sin,
+                                                           const uint8_t* __restrict__ alloc,
+                                                           const uint8_t* __restrict__ blob_g,
+                                                           uint8_t* __restrict__ actions, double* __restrict__ probs,
+                                                           uint8_t* __restrict__ out_flags) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t blob_w[];
+    __shared__ ocro::Sub subs[OC_MAX_SUBTASKS];
+    stage_roll_tables(R, blob_g, blob_w, subs);
+    const uint8_t* blob = (const uint8_t*)blob_w;
+    const int64_t P = R.pitch;
+    const int lane = (int)(threadIdx.x & (G - 1));
+    const int64_t ngroups = (int64_t)gridDim.x * (kBlock / G);
+    for (int64_t e = (int64_t)blockIdx.x * (kBlock / G) + threadIdx.x / G; e < R.B; e += ngroups) {
+        const int ai = alloc != nullptr ? alloc[e] : 0;  // group-uniform from here on
+        int f = OC_POL_BADALLOC;
+        double p = 0.0;  // p_k of this lane's candidate
+        int pick = 0, ag0 = 0, ag1 = 0;
+        bool joint = false;
+        if (ai < R.nsub) {
+            const ocro::Sub& s = subs[ai];
+            ag0 = s.agent[0];
+            ag1 = s.agent[1];
+            joint = s.n == 2;
+            const int ncand = joint ? 25 : 5;
+            ocro::RowT<K, W> r = load_row<A, K, W>(sin, P, e);
+            ocro::RowOps<A, K, W, true, GD> ops(R.L, blob, GD ? blob_g + R.L.dist_off : blob + R.L.dist_off);  // distances: LDS (narrow), device memory (wide)
+            if (OC_PT_LIK) ops.PT = R.L.pair_off != 0 ? (const uint32_t*)(blob_g + R.L.pair_off) : nullptr;
+            bool lg = false;    // this lane's candidate is legal
+            bool best = false;  // ... and its Q is the row's min (None: it is the mode)
+            f = OC_POL_RAISES;
+            if (s.kind == 0) {
+                if (!joint) {
+                    const uint32_t mv = ops.none_movable(r, ag0);
+                    double p0, p1;
+                    bool noop_mode;
+                    ops.none_probs(__builtin_popcount(mv), Q.beta, Q.nap, p0, p1, noop_mode);
+                    lg = lane == ocro::kNoop || (lane < ocro::kNoop && ((mv >> lane) & 1u));
+                    p = lane == ocro::kNoop ? p0 : (lg ? p1 : 0.0);
+                    best = lg && (lane == ocro::kNoop) == noop_mode;
+                    f = OC_POL_OK;
+                }
+            } else if (!ops.level0(r, s)) {
+                const int count = Q.mode & OC_POLICY_COUNT_STATE ? ops.goal_objects(r, s) : (int)s.count;
+                const int c0 = joint ? lane / 5 : lane, c1 = joint ? lane % 5 : ocro::kNoop;
+                lg = lane < ncand && ops.action_legal(r, s, c0, c1);
+                double q = 0.0;
+                int bad = 0, any = (int)lg;
+                if (lg) bad = (int)!ops.q_value_count(r, s, c0, c1, count, q);
+                double m = lg ? q : 1.0e300;
+#pragma unroll
+                for (int off = 1; off < G; off <<= 1) {
+                    bad |= __shfl_xor(bad, off, G);
+                    any |= __shfl_xor(any, off, G);
+                    const double o = __shfl_xor(m, off, G);
+                    m = o < m ? o : m;
+                }
+                if (any && !bad) {
+                    const double w = lg ? exp(Q.beta * (m - q)) : 0.0;
+                    double S = 0.0;  // ascending k: the sequential sum
+                    for (int c = 0; c < ncand; ++c) S += __shfl(w, c, G);
+                    p = w / S;
+                    best = lg && q == m;
+                    f = OC_POL_OK;
+                }
+            }
+            if (f == OC_POL_OK) {
+                if (Q.mode & OC_POLICY_GREEDY) {
+                    pick = best ? lane : 31;  // the lowest lane at the min
+#pragma unroll
+                    for (int off = 1; off < G; off <<= 1) {
+                        const int o = __shfl_xor(pick, off, G);
+                        pick = o < pick ? o : pick;
+                    }
+                } else {
+                    // the draw on the stored p: running sum in ascending k, the first k past u;
+                    // else (rounding) the highest legal k
+                    const double u = ocro::policy_u(Q.seed, Q.env_offset + e, Q.step, ag0);
+                    double c = 0.0;
+                    int hi = 0;
+                    pick = -1;
+                    for (int k = 0; k < ncand; ++k) {
+                        c += __shfl(p, k, G);
+                        hi = __shfl((int)lg, k, G) ? k : hi;
+                        pick = pick < 0 && u < c ? k : pick;
+                    }
+                    pick = pick < 0 ? hi : pick;
+                }
+            } else {
+                p = 0.0;
+                pick = joint ? 5 * ocro::kNoop + ocro::kNoop : ocro::kNoop;
+            }
+        }
+        if (probs != nullptr)
+            for (int k = lane; k < Q.num_cand; k += G) probs[k * P + e] = k == lane ? p : 0.0;
+        if (lane == 0) {
+            if (f != OC_POL_BADALLOC) {
+                actions[ag0 * P + e] = (uint8_t)(joint ? pick / 5 : pick);
+                if (joint) actions[ag1 * P + e] = (uint8_t)(pick % 5);
+            }
             out_flags[e] = (uint8_t)f;
         }
     }
@@ -2021,6 +2143,31 @@ static int run_ranges(int64_t nt, Fn&& fn) {
     return OC_OK;
 }
 
+// oc_cpu_nav_policy's worker: rows [e0, e1), each the whole-row ocro::RowOps::policy
+template <int A, int K, bool W>
+static void host_policy_range(const RollArgs& R, const PolicyArgs& Q, const uint8_t* blob, const uint8_t* sin,
+                              const uint8_t* alloc, uint8_t* actions, double* probs, uint8_t* out_flags, int64_t e0,
+                              int64_t e1) {
+    const int64_t P = R.pitch;
+    for (int64_t e = e0; e < e1; ++e) {
+        const int ai = alloc != nullptr ? alloc[e] : 0;
+        double p[25] = {};
+        int f = OC_POL_BADALLOC;
+        if (ai < R.nsub) {
+            const ocro::Sub& s = R.subs[ai];
+            ocro::RowOps<A, K, W, true, true> ops(R.L, blob);
+            int a0, a1;
+            f = ops.policy(load_row<A, K, W>(sin, P, e), s, Q.beta, Q.nap, Q.mode,
+                           ocro::policy_u(Q.seed, Q.env_offset + e, Q.step, s.agent[0]), p, a0, a1);
+            actions[s.agent[0] * P + e] = (uint8_t)a0;
+            if (s.n == 2) actions[s.agent[1] * P + e] = (uint8_t)a1;
+        }
+        if (probs != nullptr)
+            for (int k = 0; k < Q.num_cand; ++k) probs[k * P + e] = p[k];
+        out_flags[e] = (uint8_t)f;
+    }
+}
+
 // One launch of an n-step call: steps [r0, r0 + m) of it.
 struct StepLaunch {
     const uint8_t* src;  // the state it starts from
@@ -2131,7 +2278,7 @@ static int step_wide(const oc_handle* h, const void* sin, void* sout, const uint
 // validated subtasks.  rollout: oc_rollout's call (Level-1 configurations allowed; the
 // node-to-square table staged only for launches of one round of blocks, below).
 static int roll_args(const oc_handle* h, const oc_subtask* subtasks, int32_t num_subtasks, int64_t B, RollArgs& R,
-                     bool rollout = false) {
+                     bool rollout = false, bool host = false) {
     for (int i = 0; i < num_subtasks && subtasks != nullptr; ++i)
         if (subtasks[i].level != OC_LEVEL0 && !rollout)
             return fail(OC_EINVAL, "subtask %d: only oc_rollout takes OC_LEVEL1", i);
@@ -2139,7 +2286,7 @@ static int roll_args(const oc_handle* h, const oc_subtask* subtasks, int32_t num
     if (h->roll.nnodes < 0)
         return fail(OC_ELEVEL, "reachability graph exceeds %d nodes (a level of more than %d cells)", ocro::kMaxNodesWide,
                     ocro::kMaxCellsWide);
-    if (h->roll_blob == nullptr) return fail(OC_EHIP, "rollout tables not on the device");
+    if (h->roll_blob == nullptr && !host) return fail(OC_EHIP, "rollout tables not on the device");
     R.L = h->roll;
     R.nsub = num_subtasks;
     R.blob_words = h->roll.lds_bytes / 4;  // staged in LDS: the whole blob, or the tables before the distances
@@ -2745,6 +2892,88 @@ int oc_nav_likelihood(const oc_handle* h, const void* state, const uint8_t* take
         if (compact) return go(oc_likelihood_compact_kernel<a(), k(), 8, w(), gd()>);
         if (any_joint) return go(oc_likelihood_kernel<a(), k(), 32, w(), gd()>);
         return go(oc_likelihood_kernel<a(), k(), 8, w(), gd()>);
+    });
+}
+
+// oc_nav_policy / oc_cpu_nav_policy: the arguments both check, and the call's RollArgs / PolicyArgs
+static int policy_args(const oc_handle* h, const void* state, const oc_subtask* subtasks, int32_t num_subtasks,
+                       double beta, double nap, int32_t mode, int64_t env_offset, int64_t step, uint64_t seed,
+                       const uint8_t* actions, const double* probs, int32_t num_cand, const uint8_t* out_flags,
+                       int64_t B, bool host, RollArgs& R, PolicyArgs& Q, bool& any_joint) {
+    if (state == nullptr || subtasks == nullptr || actions == nullptr || out_flags == nullptr || B < 0 ||
+        env_offset < 0 || step < 0)
+        return fail(OC_EINVAL, "bad argument");
+    if (mode < 0 || mode > (OC_POLICY_GREEDY | OC_POLICY_COUNT_STATE)) return fail(OC_EINVAL, "policy: mode %d", mode);
+    if (num_cand != 5 && num_cand != 25) return fail(OC_EINVAL, "policy: num_cand %d (5 or 25)", num_cand);
+    if (((uintptr_t)probs & 7u) || ((uintptr_t)state & 1u)) return fail(OC_EINVAL, "misaligned buffer");
+    if (const int rc = roll_args(h, subtasks, num_subtasks, B, R, false, host)) return rc;
+    any_joint = false;
+    for (int i = 0; i < num_subtasks; ++i) any_joint |= subtasks[i].num_agents == 2;
+    if (any_joint && num_cand != 25)
+        return fail(OC_EINVAL, "policy: num_cand 5 with a two-agent configuration in the table");
+    Q.beta = beta;
+    Q.nap = nap;
+    Q.env_offset = env_offset;
+    Q.step = step;
+    Q.seed = seed;
+    Q.mode = mode;
+    Q.num_cand = num_cand;
+    return OC_OK;
+}
+
+int oc_nav_policy(const oc_handle* h, const void* state, const uint8_t* alloc, const oc_subtask* subtasks,
+                  int32_t num_subtasks, double beta, double none_action_prob, int32_t mode, int64_t env_offset,
+                  int64_t step, uint64_t seed, uint8_t* actions, double* probs, int32_t num_cand,
+                  uint8_t* out_flags, int64_t B, void* stream) {
+    if (h == nullptr) return fail(OC_EINVAL, "bad argument");
+    ErrScope es_(h);
+    OC_NEED_DEVICE(h);
+    RollArgs R;
+    PolicyArgs Q;
+    bool any_joint;
+    if (const int rc = policy_args(h, state, subtasks, num_subtasks, beta, none_action_prob, mode, env_offset, step, seed,
+                                   actions, probs, num_cand, out_flags, B, false, R, Q, any_joint))
+        return rc;
+    if (B == 0) return OC_OK;
+    // the grouped likelihood's grid: a lane group per row, up to 16 blocks per CU with 32-lane
+    // groups, 8 with 8-lane groups
+    const int64_t rows_per_block = kBlock / (any_joint ? 32 : 8);
+    const int64_t need = (B + rows_per_block - 1) / rows_per_block, cap = (int64_t)h->cus * (any_joint ? 16 : 8);
+    const dim3 grid((unsigned)(need < cap ? need : cap));
+    hipStream_t st = (hipStream_t)stream;
+    return dispatch_plan(h, [&](auto a, auto k, auto w, auto gd) {
+        auto go = [&](auto kernel) {
+            if (const int rc = allow_dyn_lds((const void*)kernel, R.blob_words * 4)) return rc;
+            hipLaunchKernelGGL(kernel, grid, dim3(kBlock), R.blob_words * 4, st, R, Q, (const uint8_t*)state, alloc,
+                               h->roll_blob, actions, probs, out_flags);
+            return hip_check("oc_nav_policy launch");
+        };
+        if (any_joint) return go(oc_policy_kernel<a(), k(), 32, w(), gd()>);
+        return go(oc_policy_kernel<a(), k(), 8, w(), gd()>);
+    });
+}
+
+int oc_cpu_nav_policy(const oc_handle* h, const void* state, const uint8_t* alloc, const oc_subtask* subtasks,
+                      int32_t num_subtasks, double beta, double none_action_prob, int32_t mode, int64_t env_offset,
+                      int64_t step, uint64_t seed, uint8_t* actions, double* probs, int32_t num_cand,
+                      uint8_t* out_flags, int64_t B, int32_t nthreads) {
+    if (h == nullptr || nthreads < 0) return fail(OC_EINVAL, "bad argument");
+    ErrScope es_(h);
+    RollArgs R;
+    PolicyArgs Q;
+    bool any_joint;
+    if (const int rc = policy_args(h, state, subtasks, num_subtasks, beta, none_action_prob, mode, env_offset, step, seed,
+                                   actions, probs, num_cand, out_flags, B, true, R, Q, any_joint))
+        return rc;
+    if (B == 0) return OC_OK;
+    const int64_t nt = host_threads(nthreads, B, 1024);  // >= 1,024 rows (up to 25 rollouts each) per thread
+    const uint8_t* blob = h->roll_blob_host.data();
+    return run_ranges(nt, [&](int64_t i) {
+        const int64_t e0 = B * i / nt, e1 = B * (i + 1) / nt;
+        return dispatch_w(h, [&](auto a, auto k, auto w) {
+            host_policy_range<a(), k(), w()>(R, Q, blob, (const uint8_t*)state, alloc, actions, probs, out_flags, e0, e1);
+            return OC_OK;
+        });
     });
 }
 

@@ -669,6 +669,28 @@ struct RowOps {
         return count > s.count;
     }
 
+    // The count is_goal compares with s.count, of the row itself: the cur_obj_count a planner
+    // gets from _define_goal_state when set_settings runs on this very state
+    // (e2e_brtdp.py:435-566; oc_nav_policy's OC_POLICY_COUNT_STATE).  None: 0.
+    OC_RH int goal_objects(const Row& r, const Sub& s) const {
+        if (s.kind == 0) return 0;
+        int count = 0;
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            const int c = r.il(j);
+            if (c == kDead || r.im(j) != s.goal) continue;
+            if (s.kind == 3) {
+                count += static_tile(c) == kDelivery ? 1 : 0;
+            } else {
+                bool dup = false;
+#pragma unroll
+                for (int i = 0; i < j; ++i) dup |= r.il(i) == c && r.im(i) == s.goal;
+                count += dup ? 0 : 1;
+            }
+        }
+        return count;
+    }
+
     OC_RH int nid(int c, int d) const {  // graph node of (cell, approach)
         return ((const uint16_t*)(T + L.node_off))[mul24((uint32_t)c, 5u) + d];
     }
@@ -1132,6 +1154,25 @@ struct RowOps {
         return true;
     }
 
+    // q_value with the goal test against `count` instead of s.count (oc_nav_policy: the table's
+    // goal_count, or the row's own goal_objects); a subtask row (s.kind != 0)
+    OC_RH bool q_value_count(const Row& r0, const Sub& s, int c0, int c1, int count, double& q) const {
+        const Target g0 = target(r0, s.agent[0], c0), g1 = s.n == 2 ? target(r0, s.agent[1], c1) : g0;
+        Row r = r0;
+        interact(r, s.agent[0], c0, g0);
+        if (s.n == 2) {
+            interact(r, s.agent[1], c1, g1);
+            if (agent_cell(r, s.agent[0]) == agent_cell(r, s.agent[1])) return false;
+        }
+        double cost = 1.0;
+        if (c0 != kNoop) cost += 0.1;
+        if (s.n == 2 && c1 != kNoop) cost += 0.1;
+        double v = 0.0;
+        if (!(goal_objects(r, s) > count)) v = (double)lower_bound(r, s) * (1.0 + 0.1) - 1.09;
+        q = cost + 1.0 * v;
+        return true;
+    }
+
     // BayesianDelegator.prob_nav_actions(..., no_level_1=True) (bayesian_delegator.py:461-689).
     // taken: agent a's executed action in byte a.  Returns OC_LIK_* flags.
     OC_RH int likelihood(Row r, const Sub& s, uint32_t taken, int self_agent, double beta, double nap,
@@ -1191,6 +1232,111 @@ struct RowOps {
         out = exp(xt - m) / S;
         return 1;
     }
+
+    // ---- oc_nav_policy: the generative side of the same agent model -------------------------
+    // The None subtask's movable actions of agent a in the full (not Level-0) state, bit c per
+    // action (what likelihood() counts).  Leaves the full-state view in this RowOps.
+    OC_RH uint32_t none_movable(const Row& r, int a) {
+        active = blockers = (1u << A) - 1u;
+        ac = kNoAc;
+        uint32_t mv = 0u;
+        for (int c = 0; c < 4; ++c) mv |= single_legal(r, a, c) ? 1u << c : 0u;
+        return mv;
+    }
+    // likelihood()'s closed form for n movable actions: p(no-op), p(each movable action), and
+    // whether the no-op is the mode (x0 >= x1).  n = 0: the no-op is certain.
+    OC_RH static void none_probs(int n, double beta, double nap, double& p0, double& p1, bool& noop_mode) {
+        p0 = 1.0;
+        p1 = 0.0;
+        noop_mode = true;
+        if (n == 0) return;
+        const double ap = (1.0 - nap) / n, x0 = beta * nap, x1 = beta * ap, m = x0 > x1 ? x0 : x1;
+        const double e0 = exp(x0 - m), e1 = exp(x1 - m);
+        double S = e0;
+        for (int k = 0; k < n; ++k) S += e1;
+        p0 = e0 / S;
+        p1 = e1 / S;
+        noop_mode = x0 >= x1;
+    }
+    // One whole row of oc_nav_policy (the host call's row; the kernel spreads the same steps over
+    // a lane group): p = the distribution over the 25 candidate slots (k = a0, or a0 * 5 + a1 for
+    // two subtask agents; illegal and unused slots +0.0), (a0, a1) the chosen action.  mode: bit 0
+    // greedy (else the draw u), bit 1 the goal count of the row's own Level-0 view.  Returns
+    // OC_POL_* flags; a raising row has all-zero p and no-ops.
+    OC_RH int policy(Row r, const Sub& s, double beta, double nap, int mode, double u, double (&p)[25], int& a0,
+                     int& a1) {
+        for (int k = 0; k < 25; ++k) p[k] = 0.0;
+        a0 = a1 = kNoop;
+        if (s.kind == 0 && s.n != 1) return 4;
+        const bool joint = s.n == 2;
+        const int ncand = joint ? 25 : 5;
+        uint32_t legal = 0u;
+        int greedy = -1;
+        if (s.kind == 0) {
+            const uint32_t mv = none_movable(r, s.agent[0]);
+            double p0, p1;
+            bool noop_mode;
+            none_probs(__builtin_popcount(mv), beta, nap, p0, p1, noop_mode);
+            legal = mv | 1u << kNoop;
+            for (int c = 0; c < 4; ++c) p[c] = (mv >> c) & 1u ? p1 : 0.0;
+            p[kNoop] = p0;
+            greedy = noop_mode ? kNoop : __builtin_ctz(mv);
+        } else {
+            if (level0(r, s)) return 4;
+            const int count = mode & 2 ? goal_objects(r, s) : (int)s.count;
+            double q[25];
+            double m = 1.0e300;
+            // kept rolled: each candidate is a whole rollout (interact + goal + bound walk)
+#pragma unroll 1
+            for (int k = 0; k < ncand; ++k) {
+                const int c0 = joint ? k / 5 : k, c1 = joint ? k % 5 : kNoop;
+                q[k] = 0.0;
+                if (!action_legal(r, s, c0, c1)) continue;
+                if (!q_value_count(r, s, c0, c1, count, q[k])) return 4;
+                legal |= 1u << k;
+                m = q[k] < m ? q[k] : m;
+            }
+            if (legal == 0u) return 4;
+            double S = 0.0;
+            for (int k = 0; k < ncand; ++k) {
+                if (!((legal >> k) & 1u)) continue;
+                p[k] = exp(beta * (m - q[k]));
+                S += p[k];
+                if (greedy < 0 && q[k] == m) greedy = k;
+            }
+            for (int k = 0; k < ncand; ++k) p[k] = p[k] / S;
+        }
+        int pick = greedy;
+        if (!(mode & 1)) pick = policy_draw(p, ncand, legal, u);
+        a0 = joint ? pick / 5 : pick;
+        a1 = joint ? pick % 5 : kNoop;
+        return 1;
+    }
+    // The draw on the returned p: the first k whose running sum (ascending k from +0.0) exceeds u,
+    // else the highest legal k.
+    OC_RH static int policy_draw(const double (&p)[25], int ncand, uint32_t legal, double u) {
+        double c = 0.0;
+        for (int k = 0; k < ncand; ++k) {
+            c += p[k];
+            if (u < c) return k;
+        }
+        return 31 - __builtin_clz(legal);
+    }
 };
+
+// oc_gen_actions' splitmix64
+OC_RH uint64_t splitmix64(uint64_t x) {
+    uint64_t z = x + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+// oc_nav_policy's uniform number of row gid at `step` for a configuration whose first agent is
+// agent0 (the tag keeps the stream apart from oc_gen_actions' and oc_reset_random's)
+OC_RH double policy_u(uint64_t seed, int64_t gid, int64_t step, int agent0) {
+    const uint64_t key = seed ^ ((uint64_t)gid * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)step * 0xC2B2AE3D27D4EB4Full) ^
+                         (uint64_t)(0x504F4C00u + (uint32_t)agent0);
+    return (double)(splitmix64(key) >> 11) * 0x1.0p-53;
+}
 
 }  // namespace ocro

@@ -39,7 +39,13 @@ EXPORTED_SYMBOLS = (
     "oc_gen_actions", "oc_state_checksum", "oc_stats_size", "oc_stats_reduce", "oc_get_last_error",
     "oc_set_likelihood_form", "oc_observe", "oc_cpu_observe", "oc_progress", "oc_cpu_progress",
     "oc_set_start_cells", "oc_get_start_cells", "oc_reset_random", "oc_cpu_reset_random",
+    "oc_nav_policy", "oc_cpu_nav_policy",
 )
+
+# oc_nav_policy: row flags, and the mode bits (bit 0 the choice, bit 1 the goal count)
+POL_OK, POL_RAISES, POL_BADALLOC = 0x01, 0x04, 0x80
+OC_POLICY_SAMPLE, OC_POLICY_GREEDY = 0, 1
+OC_POLICY_COUNT_TABLE, OC_POLICY_COUNT_STATE = 0, 2
 
 # oc_reset_random: which parts of a start are drawn (the rest keeps the level template)
 OC_START_AGENTS, OC_START_ITEMS = 1, 2
@@ -134,6 +140,22 @@ def progress_subtasks(subtasks, enc: int):
     for st in subtasks:
         kind, starts, goal = _rc.subtask_masks(st, enc)
         rows.append(subtask(kind, [0], list(starts), goal))
+    return rows
+
+
+def policy_subtasks(subtasks, enc: int, agents):
+    """oc_subtask rows for oc_nav_policy from recipe subtasks (recipes.all_subtasks(level) entries,
+    or None): each subtask as a Level-0 planner configuration of the agent indices `agents` (one
+    or two, ascending), its start and goal masks from recipes.subtask_masks in the mask encoding
+    `enc`.  goal_count stays 0: OC_POLICY_COUNT_STATE takes the count from each row's own state."""
+    from . import recipes as _rc
+    agents = sorted(int(a) for a in agents)
+    if len(agents) not in (1, 2) or len(set(agents)) != len(agents):
+        raise ValueError("policy_subtasks: one or two distinct agents, got %r" % (agents,))
+    rows = []
+    for st in subtasks:
+        kind, starts, goal = _rc.subtask_masks(st, enc)
+        rows.append(subtask(kind, agents, list(starts), goal))
     return rows
 
 
@@ -263,6 +285,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.oc_reset_random.argtypes = [vp, vp, vp, i64, i64, u64, u64, i32, vp]
     lib.oc_cpu_reset_random.restype = ctypes.c_int
     lib.oc_cpu_reset_random.argtypes = [vp, vp, vp, i64, i64, u64, u64, i32, i32]
+    lib.oc_nav_policy.restype = ctypes.c_int
+    lib.oc_nav_policy.argtypes = [vp, vp, vp, ctypes.POINTER(OcSubtask), i32, ctypes.c_double, ctypes.c_double, i32,
+                                  i64, i64, u64, vp, vp, i32, vp, i64, vp]
+    lib.oc_cpu_nav_policy.restype = ctypes.c_int
+    lib.oc_cpu_nav_policy.argtypes = [vp, vp, vp, ctypes.POINTER(OcSubtask), i32, ctypes.c_double, ctypes.c_double,
+                                      i32, i64, i64, u64, vp, vp, i32, vp, i64, i32]
     lib.oc_cpu_step.restype = ctypes.c_int
     lib.oc_cpu_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i32]
     lib.oc_step_n.restype = ctypes.c_int

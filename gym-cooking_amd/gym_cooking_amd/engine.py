@@ -295,6 +295,38 @@ class OvercookedBatch(_StartCells):
                 self_agent, beta, none_action_prob, _ptr(out), _ptr(flags), self.B, self._stream())
         return _bound(self.lib.oc_nav_likelihood, args)
 
+    def nav_policy(self, state: torch.Tensor, subtasks, actions: torch.Tensor, beta: float = 1.3,
+                   none_action_prob: float = 0.5, mode: int = capi.OC_POLICY_SAMPLE | capi.OC_POLICY_COUNT_STATE,
+                   alloc: Optional[torch.Tensor] = None, step: int = 0, seed: int = 0, env_offset: int = 0,
+                   probs: Optional[torch.Tensor] = None, num_cand: int = 25, flags: Optional[torch.Tensor] = None):
+        """Subtask-following actions (oc_nav_policy): for every row the Boltzmann distribution
+        p(a) ~ exp(-beta Q(s, a)) of its allocation's subtask agents over get_actions(s), and one
+        action from it (mode: capi.OC_POLICY_SAMPLE or OC_POLICY_GREEDY, | OC_POLICY_COUNT_TABLE or
+        OC_POLICY_COUNT_STATE) written into the subtask agents' bytes of `actions` (u8 [A][pitch];
+        every other byte stays).  `probs` (f64 [num_cand][pitch], num_cand 5 or 25) receives the
+        distribution when given.  The draw depends on (seed, step, env_offset + env) only.  Returns
+        the flags u8 [pitch] (capi.POL_*)."""
+        flags = torch.empty(self.pitch, dtype=torch.uint8, device=self.device) if flags is None else flags
+        self.nav_policy_launcher(state, subtasks, actions, beta, none_action_prob, mode, alloc, step, seed, env_offset,
+                                 probs, num_cand, flags)()
+        return flags
+
+    def nav_policy_launcher(self, state: torch.Tensor, subtasks, actions: torch.Tensor, beta: float,
+                            none_action_prob: float, mode: int, alloc: Optional[torch.Tensor], step: int, seed: int,
+                            env_offset: int, probs: Optional[torch.Tensor], num_cand: int, flags: torch.Tensor):
+        """An oc_nav_policy call bound once (see rollout_launcher)."""
+        self._check(state, self.layout.state_bytes)
+        self._check(actions, self.A * self.pitch)
+        if alloc is not None:
+            self._check(alloc, self.pitch)
+        if probs is not None:
+            self._check(probs, 8 * int(num_cand) * self.pitch, (torch.float64,))
+        self._check(flags, self.pitch)
+        args = (self._h, _ptr(state), _ptr(alloc), capi.subtask_array(subtasks), len(subtasks), float(beta),
+                float(none_action_prob), int(mode), int(env_offset), int(step), int(seed) & ((1 << 64) - 1),
+                _ptr(actions), _ptr(probs), int(num_cand), _ptr(flags), self.B, self._stream())
+        return _bound(self.lib.oc_nav_policy, args)
+
     def subtask_bounds(self, state: torch.Tensor, subtasks, lower_bound: Optional[torch.Tensor] = None,
                        doable: Optional[torch.Tensor] = None):
         """Full-state subtask bounds (oc_subtask_bounds): for every env and configuration,
@@ -526,6 +558,28 @@ class CpuStepper(_StartCells):
                                            capi.OC_OBS_F16 if dt == np.float16 else capi.OC_OBS_U8, int(view_agent),
                                            self.B, self.nthreads))
         return obs, mask
+
+    def nav_policy(self, state: np.ndarray, subtasks, actions: np.ndarray, beta: float = 1.3,
+                   none_action_prob: float = 0.5, mode: int = capi.OC_POLICY_SAMPLE | capi.OC_POLICY_COUNT_STATE,
+                   alloc: Optional[np.ndarray] = None, step: int = 0, seed: int = 0, env_offset: int = 0,
+                   probs: Optional[np.ndarray] = None, num_cand: int = 25, flags: Optional[np.ndarray] = None):
+        """oc_cpu_nav_policy: subtask-following actions in the host buffers; mirrors
+        OvercookedBatch.nav_policy.  Only the subtask agents' bytes of `actions` below column B,
+        `probs` [num_cand, pitch] and `flags` below column B are written (buffers may end at column
+        B of their last plane).  Returns the flags u8 [pitch]."""
+        B = self.B
+        flags = np.zeros(self.pitch, np.uint8) if flags is None else flags
+        for a, n, dt in ((state, self.layout.state_bytes, np.uint8), (actions, (self.A - 1) * self.pitch + B, np.uint8),
+                         (alloc, B, np.uint8), (flags, B, np.uint8),
+                         (probs, 8 * ((int(num_cand) - 1) * self.pitch + B), np.float64)):
+            if a is not None and (a.dtype != dt or not a.flags.c_contiguous or a.nbytes < n):
+                raise ValueError("host buffers: contiguous %s of at least %d bytes" % (np.dtype(dt), n))
+        p = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        capi.check(self.lib.oc_cpu_nav_policy(self._h, p(state), p(alloc), capi.subtask_array(subtasks), len(subtasks),
+                                              float(beta), float(none_action_prob), int(mode), int(env_offset),
+                                              int(step), int(seed) & ((1 << 64) - 1), p(actions), p(probs),
+                                              int(num_cand), p(flags), B, self.nthreads))
+        return flags
 
     def progress(self, state_prev: np.ndarray, states: np.ndarray, subtasks, weights=None, n: int = 1,
                  want=("counts", "events", "reward")):

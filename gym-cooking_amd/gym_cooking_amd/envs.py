@@ -908,6 +908,26 @@ class OvercookedVecEnv:
         B = self.num_envs
         return {"counts": c[0, :, :B], "events": e[0, :, :B], "reward": r[0, :B]}
 
+    def partner_actions(self, table, alloc: Optional[torch.Tensor] = None, beta: float = 1.3,
+                        mode: int = capi.OC_POLICY_SAMPLE | capi.OC_POLICY_COUNT_STATE,
+                        out: Optional[torch.Tensor] = None):
+        """Scripted-partner actions of the current states (oc_nav_policy): every env's subtask agents
+        follow the oc_subtask row `table[alloc[env]]` (capi.policy_subtasks makes the rows; `alloc`
+        u8 [pitch], None: row 0) as the reference's Boltzmann-rational agent, p(a) ~ exp(-beta Q).
+        Only those agents' bytes of `out` (u8 [A, pitch]; None: this env's buffer) are written, so a
+        learner's actions already in it survive; the draw uses the env's seed and the number of
+        step() calls so far.  Returns (the [A, B] view of `out`, flags u8 [B] of capi.POL_*)."""
+        if out is None:
+            if getattr(self, "_partner", None) is None:
+                self._partner = self.batch.new_actions()
+                self._partner_flags = torch.empty(self.P, dtype=torch.uint8, device=self.batch.device)
+            out = self._partner
+        if getattr(self, "_partner_flags", None) is None:
+            self._partner_flags = torch.empty(self.P, dtype=torch.uint8, device=self.batch.device)
+        self.batch.nav_policy(self.state, table, out, beta=beta, mode=mode, alloc=alloc, step=self._round,
+                              seed=self.seed, flags=self._partner_flags)
+        return out.view(self.A, self.P)[:, :self.num_envs], self._partner_flags[:self.num_envs]
+
     def episode_stats(self) -> torch.Tensor:
         """int64 [episodes, successes, steps, collisions, errors] since construction."""
         return self.batch.reduce_stats(self.stats)

@@ -18,6 +18,9 @@
  *   oc_reset_random, oc_cpu_reset_random, oc_set_start_cells, oc_get_start_cells
  *                            <- load_level (:144-193) + reset (:201-250) of the level file with its item
  *                               letters and spawn lines moved, per env
+ *   oc_nav_policy, oc_cpu_nav_policy <- a Boltzmann-rational agent following a subtask: the action model
+ *                               BayesianDelegator.prob_nav_actions scores
+ *                               (gym_cooking/delegation_planner/bayesian_delegator.py:461-689), sampled
  *   oc_gen_actions           <- synthetic action streams (the reference env has no RNG)
  *   oc_stats_*               <- the per-episode bookkeeping main.py keeps in its metrics Bag
  *                               (gym_cooking/misc/metrics/metrics_bag.py:40-72), reduced per GPU
@@ -634,6 +637,77 @@ int oc_reset_random(const oc_handle* h, void* state, const void* state_prev, int
  * written.  It never touches the device; oc_reset_random never calls it. */
 int oc_cpu_reset_random(const oc_handle* h, void* state, const void* state_prev, int64_t B, int64_t env_offset,
                         uint64_t seed, uint64_t round, int32_t what, int32_t nthreads);
+
+/* ---------------------------------------------------------------------------------------
+ * Subtask-following actions (additive to ABI 12): the generative side of oc_nav_likelihood's
+ * agent model, for a scripted partner.  Per row, the whole Boltzmann distribution over
+ * get_actions(s) under the row's planner configuration, and one action taken from it:
+ *   p(a | s, subtask) ~ exp(-beta * Q(s, a)),  Q as oc_nav_likelihood's (a fresh planner's
+ *   value_init values; bayesian_delegator.py:461-689, e2e_brtdp.py:678-760).
+ * Candidate k is a0 for a one-agent configuration and a0 * 5 + a1 for two agents (the
+ * likelihood's order); it is legal iff the action is in get_actions on the row's Level-0 view.
+ * There is no self agent and no taken action: a joint configuration gets the full 25-way
+ * distribution.  For a subtask row that does not raise, in f64:
+ *   m = min of Q_k over the legal k;  w_k = exp(beta * (m - Q_k));
+ *   S = the w_k of the legal k added in ascending k, starting from +0.0;
+ *   p_k = w_k / S;  illegal candidates have p_k = +0.0.
+ * OC_SUB_NONE with one agent a: the likelihood's closed form with a as both the self agent and
+ * the acting agent: n = a's movable actions in the full state, x0 = beta * nap,
+ * x1 = beta * ((1 - nap) / n), mm = max(x0, x1), S = exp(x0 - mm) then n adds of exp(x1 - mm),
+ * p(no-op) = exp(x0 - mm) / S, p of each movable action = exp(x1 - mm) / S; n = 0: p(no-op) = 1.0
+ * and the row is OK.
+ * mode bit 1, the count is_goal_state compares with: OC_POLICY_COUNT_TABLE the configuration's
+ * goal_count; OC_POLICY_COUNT_STATE the number of goal objects in the row's own Level-0 view, the
+ * cur_obj_count a planner gets from _define_goal_state when set_settings runs on this very state
+ * (e2e_brtdp.py:435-566): a partner that was "configured now", right for a batch whose envs are
+ * at different points of a recipe.
+ * mode bit 0, the choice: OC_POLICY_GREEDY the lowest legal k with Q_k == m (None: the no-op if
+ * x0 >= x1 or n = 0, else the lowest movable action).  OC_POLICY_SAMPLE one number per row:
+ *   key = seed ^ gid * 0x9E3779B97F4A7C15 ^ step * 0xC2B2AE3D27D4EB4F ^ (0x504F4C00 + agent[0]),
+ *   gid = env_offset + e (identical for any split of the envs over GPUs, as oc_gen_actions),
+ *   u = (splitmix64(key) >> 11) * 2^-53;  c = +0.0; for k = 0 .. ncand - 1 ascending (ncand = 5
+ *   or 25, the row's own): c += p_k, the first k with u < c is taken; if rounding leaves none,
+ *   the highest legal k.  The draw is defined on the p values the call returns: a caller can
+ *   replay it exactly from `probs`.
+ * ------------------------------------------------------------------------------------- */
+#define OC_POL_OK 0x01        /* distribution computed, action written */
+#define OC_POL_RAISES 0x04    /* the reference raises: two removed agents on one square (Level-0
+                                 configuration), a legal joint candidate whose T ends co-located,
+                                 None for two agents, or no legal candidate */
+#define OC_POL_BADALLOC 0x80  /* alloc id >= num_subtasks */
+#define OC_POLICY_SAMPLE 0      /* mode bit 0 */
+#define OC_POLICY_GREEDY 1
+#define OC_POLICY_COUNT_TABLE 0 /* mode bit 1: goal test against the table's goal_count */
+#define OC_POLICY_COUNT_STATE 2 /* ... against the row's own count */
+
+/*   state, alloc, subtasks, num_subtasks, beta, none_action_prob : as oc_nav_likelihood
+ *                (OC_LEVEL0 configurations only; alloc NULL: subtasks[0])
+ *   env_offset, step (>= 0), seed : the draw's
+ *   actions    : u8 [A][pitch], required.  Only the bytes of row e's subtask agents are written,
+ *                with the chosen a0 / a1 (OC_ACT_NOOP on OC_POL_RAISES rows, nothing on
+ *                OC_POL_BADALLOC rows); every other agent's byte and every column >= B stays
+ *                untouched, so a learner's actions in the same buffer survive
+ *   probs      : nullable; f64 [num_cand][pitch], 8-byte aligned, plane k = p_k.  num_cand is 5
+ *                or 25; 5 with a two-agent configuration in the table is OC_EINVAL.  A one-agent
+ *                row of a 25-candidate call fills planes 0..4 and zeroes the rest; rows that are
+ *                not OK are all zero; columns >= B are untouched
+ *   out_flags  : u8 [pitch] OC_POL_*, required; columns >= B untouched
+ * Stream-ordered, no allocation, no synchronisation (hipGraph-capturable, as oc_step).  Bad
+ * arguments and host-only handles are OC_EINVAL. */
+int oc_nav_policy(const oc_handle* h, const void* state, const uint8_t* alloc, const oc_subtask* subtasks,
+                  int32_t num_subtasks, double beta, double none_action_prob, int32_t mode, int64_t env_offset,
+                  int64_t step, uint64_t seed, uint8_t* actions, double* probs, int32_t num_cand,
+                  uint8_t* out_flags, int64_t B, void* stream);
+
+/* The same on the host (what oc_cpu_step is to oc_step): HOST buffers, works on OC_DEVICE_HOST
+ * handles, the kernel's row functions compiled for the host, threaded over env ranges (nthreads
+ * 0 = the host's hardware threads; at least 1,024 rows each).  Nothing past column B is
+ * written.  It never touches the device; oc_nav_policy never calls it.  The two agree on flags
+ * and, up to the last bits of exp and of a fused multiply-add, on probs. */
+int oc_cpu_nav_policy(const oc_handle* h, const void* state, const uint8_t* alloc, const oc_subtask* subtasks,
+                      int32_t num_subtasks, double beta, double none_action_prob, int32_t mode, int64_t env_offset,
+                      int64_t step, uint64_t seed, uint8_t* actions, double* probs, int32_t num_cand,
+                      uint8_t* out_flags, int64_t B, int32_t nthreads);
 
 #ifdef __cplusplus
 }
