@@ -1388,6 +1388,37 @@ __global__ __launch_bounds__(kBlock) void oc_bounds_kernel(RollArgs R, const uin
     }
 }
 
+// Per-env subtask choice of scripted agents (oc_task_select), a sibling of oc_bounds_kernel: one
+// env per lane, the tables and the M x S one-agent configurations staged as there, bound_row
+// built once per env.  Where the bounds kernel evaluates every configuration and writes 5 bytes
+// for each, this one walks only the subtasks some lane of the wave still has in its incomplete set
+// (ocro::RowOps::task_env) and reads and writes the agents' few task-state planes; every plane
+// access of a wave covers 64 consecutive envs of one plane.  The agents of an env run in order on
+// its lane (OC_TASK_DISTINCT makes agent m's candidates depend on agent m - 1's choice), so the
+// launch is not chunked over configurations.
+struct TaskArgs {
+    int32_t S, M, flags;
+};
+template <int A, int K, bool W, bool GD>
+__global__ __launch_bounds__(kBlock) void oc_task_kernel(RollArgs R, TaskArgs Q, const uint8_t* __restrict__ sin,
+                                                         const uint8_t* __restrict__ sprev,
+                                                         const uint8_t* __restrict__ blob_g, uint8_t* __restrict__ ts,
+                                                         float* __restrict__ bound, uint8_t* __restrict__ info) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t blob_w[];
+    __shared__ ocro::Sub subs[OC_MAX_SUBTASKS];
+    stage_roll_tables(R, blob_g, blob_w, subs);
+    const uint8_t* blob = (const uint8_t*)blob_w;
+    const int64_t P = R.pitch;
+    using PL = Planes<A, K, W>;
+    for (int64_t e = blockIdx.x * (int64_t)kBlock + threadIdx.x; e < R.B; e += (int64_t)gridDim.x * kBlock) {
+        const ocro::RowT<K, W> r = load_row<A, K, W>(sin, P, e);
+        const bool init = (Q.flags & OC_TASK_INIT) != 0 || (sprev != nullptr && (sprev[PL::F * P + e] & OC_FLAG_DONE) != 0);
+        ocro::RowOps<A, K, W, false, GD> ops(R.L, blob, GD ? blob_g + R.L.dist_off : blob + R.L.dist_off);  // distances: LDS (narrow), device memory (wide)
+        ops.task_env(r, subs, Q.S, Q.M, Q.flags, init, ts + e, bound != nullptr ? bound + e : nullptr,
+                     info != nullptr ? info + e : nullptr, P);
+    }
+}
+
 // ---- wide levels (more than 255 cells: u16 cell ids) ----------------------------------------
 // A wide level (more than 255 cells, u16 cell ids) is stepped by ocsw::step4w: the SWAR step
 // with every cell-valued quantity as two byte words (its low and high bytes, the wide layout's
@@ -3011,6 +3042,99 @@ int oc_subtask_bounds(const oc_handle* h, const void* state, const oc_subtask* s
         hipLaunchKernelGGL(kernel, grid, dim3(kBlock), R.blob_words * 4, st, R, (const uint8_t*)state, h->roll_blob,
                            lower_bound, doable);
         return hip_check("oc_subtask_bounds launch");
+    });
+}
+
+// oc_task_select / oc_cpu_task_select: the arguments both check, and the call's RollArgs (agent
+// m's S one-agent Level-0 configurations at rows m * S ..) and TaskArgs
+static int task_args(const oc_handle* h, const void* state, const oc_subtask* subtasks, int32_t num_subtasks,
+                     const uint8_t* agents, int32_t num_scripted, int32_t flags, const uint8_t* tstate,
+                     const float* bound, int64_t B, bool host, RollArgs& R, TaskArgs& Q) {
+    if (state == nullptr || subtasks == nullptr || agents == nullptr || tstate == nullptr)
+        return fail(OC_EINVAL, "task_select: state, subtasks, agents and tstate are required");
+    if (B < 0) return fail(OC_EINVAL, "task_select: B %lld", (long long)B);
+    const int32_t S = num_subtasks, M = num_scripted;
+    if (M < 1 || M > h->A) return fail(OC_EINVAL, "task_select: num_scripted %d (1..%d)", M, h->A);
+    if (S < 1 || S > 63) return fail(OC_EINVAL, "task_select: num_subtasks %d (1..63)", S);
+    if (M * S > OC_MAX_SUBTASKS)
+        return fail(OC_EINVAL, "task_select: num_scripted x num_subtasks = %d (at most %d)", M * S, OC_MAX_SUBTASKS);
+    if (flags < 0 || flags > (OC_TASK_INIT | OC_TASK_COMMIT | OC_TASK_DISTINCT))
+        return fail(OC_EINVAL, "task_select: flags %d", flags);
+    for (int m = 0; m < M; ++m) {
+        if (agents[m] >= h->A) return fail(OC_EINVAL, "task_select: agent %d", agents[m]);
+        for (int q = 0; q < m; ++q)
+            if (agents[q] == agents[m]) return fail(OC_EINVAL, "task_select: agent %d listed twice", agents[m]);
+    }
+    if (((uintptr_t)bound & 3u) || ((uintptr_t)state & 1u)) return fail(OC_EINVAL, "task_select: misaligned buffer");
+    oc_subtask rows[OC_MAX_SUBTASKS];
+    for (int m = 0; m < M; ++m)
+        for (int i = 0; i < S; ++i) {
+            oc_subtask& d = rows[m * S + i];
+            d = oc_subtask{};
+            d.kind = subtasks[i].kind;
+            d.num_agents = 1;
+            d.agent[0] = agents[m];
+            d.start_mask[0] = subtasks[i].start_mask[0];
+            d.start_mask[1] = subtasks[i].start_mask[1];
+            d.goal_mask = subtasks[i].goal_mask;
+            d.level = OC_LEVEL0;
+        }
+    if (const int rc = roll_args(h, rows, M * S, B, R, false, host)) return rc;
+    Q.S = S;
+    Q.M = M;
+    Q.flags = flags;
+    return OC_OK;
+}
+
+int oc_task_select(const oc_handle* h, const void* state, const void* state_prev, const oc_subtask* subtasks,
+                   int32_t num_subtasks, const uint8_t* agents, int32_t num_scripted, int32_t flags, uint8_t* tstate,
+                   float* bound, uint8_t* info, int64_t B, void* stream) {
+    if (h == nullptr) return fail(OC_EINVAL, "bad argument");
+    ErrScope es_(h);
+    OC_NEED_DEVICE(h);
+    RollArgs R;
+    TaskArgs Q;
+    if (const int rc = task_args(h, state, subtasks, num_subtasks, agents, num_scripted, flags, tstate, bound, B, false, R, Q))
+        return rc;
+    if (B == 0) return OC_OK;
+    const int64_t need = (B + kBlock - 1) / kBlock, cap = (int64_t)h->cus * 8;
+    const dim3 grid((unsigned)(need < cap ? need : cap));
+    hipStream_t st = (hipStream_t)stream;
+    return dispatch_plan(h, [&](auto a, auto k, auto w, auto gd) {
+        const auto kernel = oc_task_kernel<a(), k(), w(), gd()>;
+        if (const int rc = allow_dyn_lds((const void*)kernel, R.blob_words * 4)) return rc;
+        hipLaunchKernelGGL(kernel, grid, dim3(kBlock), R.blob_words * 4, st, R, Q, (const uint8_t*)state,
+                           (const uint8_t*)state_prev, h->roll_blob, tstate, bound, info);
+        return hip_check("oc_task_select launch");
+    });
+}
+
+int oc_cpu_task_select(const oc_handle* h, const void* state, const void* state_prev, const oc_subtask* subtasks,
+                       int32_t num_subtasks, const uint8_t* agents, int32_t num_scripted, int32_t flags,
+                       uint8_t* tstate, float* bound, uint8_t* info, int64_t B, int32_t nthreads) {
+    if (h == nullptr || nthreads < 0) return fail(OC_EINVAL, "bad argument");
+    ErrScope es_(h);
+    RollArgs R;
+    TaskArgs Q;
+    if (const int rc = task_args(h, state, subtasks, num_subtasks, agents, num_scripted, flags, tstate, bound, B, true, R, Q))
+        return rc;
+    if (B == 0) return OC_OK;
+    const int64_t nt = host_threads(nthreads, B, 1024);  // >= 1,024 rows (up to M x S bound walks each) per thread
+    const uint8_t* blob = h->roll_blob_host.data();
+    const uint8_t *sin = (const uint8_t*)state, *sprev = (const uint8_t*)state_prev;
+    return run_ranges(nt, [&](int64_t i) {
+        const int64_t e0 = B * i / nt, e1 = B * (i + 1) / nt;
+        return dispatch_w(h, [&](auto a, auto k, auto w) {
+            using PL = Planes<a(), k(), w()>;
+            const int64_t P = R.pitch;
+            for (int64_t e = e0; e < e1; ++e) {
+                const bool init = (Q.flags & OC_TASK_INIT) != 0 || (sprev != nullptr && (sprev[PL::F * P + e] & OC_FLAG_DONE) != 0);
+                ocro::RowOps<a(), k(), w(), false, true> ops(R.L, blob);
+                ops.task_env(load_row<a(), k(), w()>(sin, P, e), R.subs, Q.S, Q.M, Q.flags, init, tstate + e,
+                             bound != nullptr ? bound + e : nullptr, info != nullptr ? info + e : nullptr, P);
+            }
+            return OC_OK;
+        });
     });
 }
 

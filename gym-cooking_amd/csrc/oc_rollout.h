@@ -1322,6 +1322,88 @@ struct RowOps {
         }
         return 31 - __builtin_clz(legal);
     }
+
+    // ---- oc_task_select: a scripted agent's subtask bookkeeping and greedy choice ------------
+    // A held item's cell becomes its holder's square (the lowest agent that names the live slot),
+    // as oc_progress counts it (agent.py:408-423): goal_objects on the result is oc_progress's
+    // count_i.  The bounds do not read a held slot's cell (bound_row's avail leaves it out).
+    OC_RH void hold_cells(Row& r) const {
+#pragma unroll
+        for (int a = A - 1; a >= 0; --a) {
+            const int h = r.ah(a);
+            if (h < K && r.il(h) != kDead) r.set_loc(h, (uint32_t)agent_cell(r, a));
+        }
+    }
+    // One env of oc_task_select (include/oc_engine.h, "The rule"): the scripted agents m < M in the
+    // caller's order, agent m's one-agent configurations in subs[m * S .. m * S + S).  ts / bound /
+    // info point at column e of the call's buffers (planes P apart); each agent's task state is
+    // read before it is written.  refresh_subtasks (utils/agent.py:151-171), then the smallest
+    // bound over the doable incomplete subtasks (add_greedy_subtasks -> prune_subtask_allocs,
+    // bayesian_delegator.py:892-923, :200-256).  A subtask no lane of the wave has in its
+    // incomplete set costs no bound walk (wave_any; every lane of the host build is its own wave).
+    OC_RH void task_env(Row r, const Sub* subs, int S, int M, int flags, bool init, uint8_t* ts, float* bound,
+                        uint8_t* info, int64_t P) {
+        const int EP = (S + 7) >> 3, TP = EP + 2;
+        hold_cells(r);
+        const BoundRow br = bound_row<true>(r);
+        uint64_t taken = 0ull;  // OC_TASK_DISTINCT: the subtasks the earlier scripted agents hold
+#pragma unroll 1
+        for (int m = 0; m < M; ++m) {
+            const Sub* sm = subs + m * S;
+            uint8_t* tm = ts + (int64_t)m * TP * P;
+            uint64_t inc = 0ull;
+            for (int c = 0; c < EP; ++c) inc |= (uint64_t)tm[c * P] << (8 * c);
+            inc &= (1ull << S) - 1ull;
+            int cur = tm[EP * P], cnt = tm[(EP + 1) * P], fl = 0;
+            if (init) {
+                inc = (1ull << S) - 1ull;
+                cur = S;
+                cnt = 0;
+                fl = 4;  // OC_TASKF_REINIT
+            }
+            const int entry = cur;
+            // refresh: the current subtask's count rose (evaluated on every lane, used where cur < S)
+            const int now = goal_objects(r, sm[cur < S ? cur : 0]);
+            if (cur < S && now > cnt) {
+                inc &= ~(1ull << cur);
+                cur = S;
+                fl |= 1;  // OC_TASKF_COMPLETED
+            }
+            int pick = S;
+            float best = 0.0f, keep_lb = 0.0f;
+            bool keep = false;
+#pragma unroll 1
+            for (int i = 0; i < S; ++i) {
+                const Sub& s = sm[i];
+                const bool want = ((inc >> i) & 1ull) != 0ull && s.kind != 0 && ((taken >> i) & 1ull) == 0ull;
+                if (!wave_any(want)) continue;  // wave-uniform
+                float lb;
+                const bool cand = full_bound(br, r, s, lb) && want;
+                if (cand && (pick == S || lb < best)) {
+                    pick = i;
+                    best = lb;
+                }
+                if (cand && i == cur) {
+                    keep = true;
+                    keep_lb = lb;
+                }
+            }
+            if ((flags & 2) && keep) {  // OC_TASK_COMMIT: cur is still a candidate
+                pick = cur;
+                best = keep_lb;
+            }
+            const int fresh = goal_objects(r, sm[pick < S ? pick : 0]);
+            if (pick != cur && pick < S) cnt = fresh;
+            cur = pick;
+            if (cur != entry) fl |= 2;  // OC_TASKF_SWITCHED
+            if ((flags & 4) && cur < S) taken |= 1ull << cur;  // OC_TASK_DISTINCT
+            for (int c = 0; c < EP; ++c) tm[c * P] = (uint8_t)(inc >> (8 * c));
+            tm[EP * P] = (uint8_t)cur;
+            tm[(EP + 1) * P] = (uint8_t)cnt;
+            if (bound != nullptr) bound[m * P] = cur < S ? best : 0.0f;
+            if (info != nullptr) info[m * P] = (uint8_t)fl;
+        }
+    }
 };
 
 // oc_gen_actions' splitmix64

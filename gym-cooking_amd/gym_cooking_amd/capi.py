@@ -39,8 +39,12 @@ EXPORTED_SYMBOLS = (
     "oc_gen_actions", "oc_state_checksum", "oc_stats_size", "oc_stats_reduce", "oc_get_last_error",
     "oc_set_likelihood_form", "oc_observe", "oc_cpu_observe", "oc_progress", "oc_cpu_progress",
     "oc_set_start_cells", "oc_get_start_cells", "oc_reset_random", "oc_cpu_reset_random",
-    "oc_nav_policy", "oc_cpu_nav_policy",
+    "oc_nav_policy", "oc_cpu_nav_policy", "oc_task_select", "oc_cpu_task_select",
 )
+
+# oc_task_select: call flags, and the per-agent info bits
+OC_TASK_INIT, OC_TASK_COMMIT, OC_TASK_DISTINCT = 1, 2, 4
+TASKF_COMPLETED, TASKF_SWITCHED, TASKF_REINIT = 0x01, 0x02, 0x04
 
 # oc_nav_policy: row flags, and the mode bits (bit 0 the choice, bit 1 the goal count)
 POL_OK, POL_RAISES, POL_BADALLOC = 0x01, 0x04, 0x80
@@ -65,6 +69,12 @@ def event_planes(n: int) -> int:
     """Byte planes of oc_progress's events for n subtasks (OC_PROGRESS_EVENT_PLANES): bit b of
     plane c is subtask 8c + b."""
     return (n + 7) // 8
+
+
+def task_planes(S: int) -> int:
+    """Byte planes of one scripted agent's oc_task_select state for S subtasks (OC_TASK_PLANES):
+    the incomplete set (event_planes(S) planes), then cur, then cnt."""
+    return event_planes(S) + 2
 
 
 class OcLevelDesc(ctypes.Structure):
@@ -291,6 +301,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.oc_cpu_nav_policy.restype = ctypes.c_int
     lib.oc_cpu_nav_policy.argtypes = [vp, vp, vp, ctypes.POINTER(OcSubtask), i32, ctypes.c_double, ctypes.c_double,
                                       i32, i64, i64, u64, vp, vp, i32, vp, i64, i32]
+    lib.oc_task_select.restype = ctypes.c_int
+    lib.oc_task_select.argtypes = [vp, vp, vp, ctypes.POINTER(OcSubtask), i32, vp, i32, i32, vp, vp, vp, i64, vp]
+    lib.oc_cpu_task_select.restype = ctypes.c_int
+    lib.oc_cpu_task_select.argtypes = [vp, vp, vp, ctypes.POINTER(OcSubtask), i32, vp, i32, i32, vp, vp, vp, i64, i32]
     lib.oc_cpu_step.restype = ctypes.c_int
     lib.oc_cpu_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i32]
     lib.oc_step_n.restype = ctypes.c_int

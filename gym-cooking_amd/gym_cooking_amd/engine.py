@@ -327,6 +327,46 @@ class OvercookedBatch(_StartCells):
                 _ptr(actions), _ptr(probs), int(num_cand), _ptr(flags), self.B, self._stream())
         return _bound(self.lib.oc_nav_policy, args)
 
+    def new_task_state(self, S: int, M: int) -> torch.Tensor:
+        """u8 [M, capi.task_planes(S), pitch] task state of M scripted agents over S subtasks
+        (oc_task_select), zeroed; the first call on it passes capi.OC_TASK_INIT."""
+        return torch.zeros((M, capi.task_planes(S), self.pitch), dtype=torch.uint8, device=self.device)
+
+    def task_select(self, state: torch.Tensor, subtasks, agents, tstate: torch.Tensor,
+                    prev: Optional[torch.Tensor] = None, flags: int = capi.OC_TASK_COMMIT | capi.OC_TASK_DISTINCT,
+                    bound: Optional[torch.Tensor] = None, info: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Per-env subtask choice of the scripted agents `agents` (oc_task_select): the reference
+        agent's refresh_subtasks over `tstate` (new_task_state; updated in place) and the doable
+        incomplete subtask with the smallest lower bound, per agent in the given order.  `subtasks`
+        are oc_subtask rows (capi.progress_subtasks; kind, start and goal masks are read).  The cur
+        plane tstate[m, capi.event_planes(S)] is nav_policy's `alloc` for agent m's table
+        capi.policy_subtasks(subtasks + [None], enc, [agent]).  With `prev` (the state before the
+        step that made `state`) the envs that step auto-reset start over; capi.OC_TASK_INIT in
+        `flags` starts every env over.  `bound` (f32 [M, pitch]) receives the chosen bounds when
+        given.  Returns info u8 [M, pitch] (capi.TASKF_*)."""
+        if info is None:
+            info = torch.empty((len(agents), self.pitch), dtype=torch.uint8, device=self.device)
+        self.task_select_launcher(state, subtasks, agents, tstate, prev, flags, bound, info)()
+        return info
+
+    def task_select_launcher(self, state: torch.Tensor, subtasks, agents, tstate: torch.Tensor,
+                             prev: Optional[torch.Tensor], flags: int, bound: Optional[torch.Tensor],
+                             info: Optional[torch.Tensor]):
+        """An oc_task_select call bound once (see rollout_launcher)."""
+        S, M = len(subtasks), len(agents)
+        self._check(state, self.layout.state_bytes)
+        if prev is not None:
+            self._check(prev, self.layout.state_bytes)
+        self._check(tstate, M * capi.task_planes(S) * self.pitch)
+        if bound is not None:
+            self._check(bound, 4 * M * self.pitch, (torch.float32,))
+        if info is not None:
+            self._check(info, M * self.pitch)
+        ags = (ctypes.c_uint8 * M)(*[int(a) for a in agents])
+        args = (self._h, _ptr(state), _ptr(prev), capi.subtask_array(subtasks), S, ags, M, int(flags), _ptr(tstate),
+                _ptr(bound), _ptr(info), self.B, self._stream())
+        return _bound(self.lib.oc_task_select, args)
+
     def subtask_bounds(self, state: torch.Tensor, subtasks, lower_bound: Optional[torch.Tensor] = None,
                        doable: Optional[torch.Tensor] = None):
         """Full-state subtask bounds (oc_subtask_bounds): for every env and configuration,
@@ -580,6 +620,26 @@ class CpuStepper(_StartCells):
                                               int(step), int(seed) & ((1 << 64) - 1), p(actions), p(probs),
                                               int(num_cand), p(flags), B, self.nthreads))
         return flags
+
+    def task_select(self, state: np.ndarray, subtasks, agents, tstate: np.ndarray,
+                    prev: Optional[np.ndarray] = None, flags: int = capi.OC_TASK_COMMIT | capi.OC_TASK_DISTINCT,
+                    bound: Optional[np.ndarray] = None, info: Optional[np.ndarray] = None) -> np.ndarray:
+        """oc_cpu_task_select: the scripted agents' subtask choice in the host buffers; mirrors
+        OvercookedBatch.task_select.  `tstate` u8 [M, capi.task_planes(S), pitch] is updated in place,
+        `bound` f32 [M, pitch] when given; only columns below B are written (buffers may end at
+        column B of their last plane).  Returns info u8 [M, pitch]."""
+        S, M, B, P = len(subtasks), len(agents), self.B, self.pitch
+        info = np.zeros((M, P), np.uint8) if info is None else info
+        for a, n, dt in ((state, self.layout.state_bytes, np.uint8), (prev, self.layout.state_bytes, np.uint8),
+                         (tstate, (M * capi.task_planes(S) - 1) * P + B, np.uint8), (info, (M - 1) * P + B, np.uint8),
+                         (bound, 4 * ((M - 1) * P + B), np.float32)):
+            if a is not None and (a.dtype != dt or not a.flags.c_contiguous or a.nbytes < n):
+                raise ValueError("host buffers: contiguous %s of at least %d bytes" % (np.dtype(dt), n))
+        p = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        ags = (ctypes.c_uint8 * M)(*[int(a) for a in agents])
+        capi.check(self.lib.oc_cpu_task_select(self._h, p(state), p(prev), capi.subtask_array(subtasks), S, ags, M,
+                                               int(flags), p(tstate), p(bound), p(info), B, self.nthreads))
+        return info
 
     def progress(self, state_prev: np.ndarray, states: np.ndarray, subtasks, weights=None, n: int = 1,
                  want=("counts", "events", "reward")):

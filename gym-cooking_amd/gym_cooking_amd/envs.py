@@ -843,6 +843,7 @@ class OvercookedVecEnv:
         if self.random_starts:
             self.batch.reset_random(self.state, None, self.seed, self._round, self.random_starts)
         self._stepped = False
+        self._task_round = None  # partner_tasks(): the next call starts every env over
         return self.state
 
     def step(self, actions: torch.Tensor):
@@ -927,6 +928,57 @@ class OvercookedVecEnv:
         self.batch.nav_policy(self.state, table, out, beta=beta, mode=mode, alloc=alloc, step=self._round,
                               seed=self.seed, flags=self._partner_flags)
         return out.view(self.A, self.P)[:, :self.num_envs], self._partner_flags[:self.num_envs]
+
+    def partner_tasks(self, agents, commit: bool = True, distinct: bool = True):
+        """The subtask each scripted agent of `agents` (indices, in priority order) follows in the
+        current states (oc_task_select over ``subtasks``): per env the reference agent's
+        refresh_subtasks and then the doable incomplete subtask with the smallest lower bound;
+        `commit` keeps the current one while it stays a candidate, `distinct` keeps two scripted
+        agents off one subtask.  The task state lives in this env across step(): the first call
+        after reset() (or with other agents) starts every env over, a call after a step starts over
+        the envs that step auto-reset, and a second call on the same states starts none.  Returns
+        (cur u8 [M, B]: the subtask index, len(subtasks) for None; info u8 [M, B] of capi.TASKF_*),
+        views of this env's buffers."""
+        agents = tuple(int(a) for a in agents)
+        S = len(self.subtasks)
+        if S == 0:
+            raise ValueError("the level's recipes have no subtasks")
+        M, EP = len(agents), capi.event_planes(S)
+        flags = (capi.OC_TASK_COMMIT if commit else 0) | (capi.OC_TASK_DISTINCT if distinct else 0)
+        if getattr(self, "_task_agents", None) != agents:
+            self._task_agents = agents
+            self._task = self.batch.new_task_state(S, M)
+            self._task_info = torch.empty((M, self.P), dtype=torch.uint8, device=self.batch.device)
+            self._task_round = None
+        prev = None
+        if self._task_round is None:
+            flags |= capi.OC_TASK_INIT
+        elif self._task_round != self._round:  # stepped since: the other buffer is the state before
+            prev = self._s[self._i ^ 1]
+        self._task_round = self._round
+        self.batch.task_select(self.state, self._sub_rows, agents, self._task, prev, flags, None, self._task_info)
+        B = self.num_envs
+        return self._task[:, EP, :B], self._task_info[:, :B]
+
+    def scripted_actions(self, agents, beta: float = 1.3,
+                         mode: int = capi.OC_POLICY_SAMPLE | capi.OC_POLICY_COUNT_STATE,
+                         out: Optional[torch.Tensor] = None, commit: bool = True, distinct: bool = True):
+        """Actions of scripted partners that drive themselves: partner_tasks(agents) picks each
+        agent's subtask per env, then partner_actions runs once per agent with that agent's
+        one-agent table (the level's subtasks, then None) and its cur plane as `alloc`.  Only the
+        scripted agents' bytes of `out` (u8 [A, pitch]; None: this env's buffer) are written.
+        Returns (the [A, B] view of `out`, task info u8 [M, B])."""
+        agents = tuple(int(a) for a in agents)
+        _, info = self.partner_tasks(agents, commit, distinct)
+        tables = self.__dict__.setdefault("_task_tables", {})
+        EP = capi.event_planes(len(self.subtasks))
+        view = None
+        for m, a in enumerate(agents):
+            if a not in tables:
+                tables[a] = capi.policy_subtasks(list(self.subtasks) + [None], self.batch.level.encoding, [a])
+            view, _ = self.partner_actions(tables[a], self._task[m, EP], beta, mode, out)
+            out = self._partner if out is None else out
+        return view, info
 
     def episode_stats(self) -> torch.Tensor:
         """int64 [episodes, successes, steps, collisions, errors] since construction."""

@@ -709,6 +709,82 @@ int oc_cpu_nav_policy(const oc_handle* h, const void* state, const uint8_t* allo
                       int64_t step, uint64_t seed, uint8_t* actions, double* probs, int32_t num_cand,
                       uint8_t* out_flags, int64_t B, int32_t nthreads);
 
+/* ---------------------------------------------------------------------------------------
+ * Per-env subtask choice for scripted agents (additive to ABI 12): the byte oc_nav_policy's
+ * `alloc` takes, made on the device.  Per env and scripted agent, the reference agent's subtask
+ * bookkeeping and a greedy delegator's choice over the pruned hypothesis space:
+ *   refresh_subtasks, def_subtask_completion, is_subtask_complete
+ *                                   gym_cooking/utils/agent.py:151-171, 286-368
+ *   add_greedy_subtasks             delegation_planner/bayesian_delegator.py:892-923
+ *   prune_subtask_allocs            bayesian_delegator.py:200-256
+ *   subtask_alloc_is_doable         bayesian_delegator.py:98-156
+ *   add_dc_subtasks (no two agents on one subtask: OC_TASK_DISTINCT)   bayesian_delegator.py:928-1000
+ * Build-defined, like auto-reset, oc_reset_random and oc_nav_policy's fresh-planner Q: only the
+ * ranking is this build's, the smallest get_lower_bound_for_subtask_given_objs, which orders the
+ * candidates as 1 / (1.1 * lb - 1.09) does wherever that is positive.  It is not set_priors: the
+ * reference ranks allocations by 1 / v_l read after a BRTDP search (bayesian_delegator.py:162-194,
+ * 296-369), and its Bayesian updates over time are not restated either.
+ *
+ * The rule, for env e and the scripted agents m = 0 .. M-1 in the caller's order, a = agents[m]:
+ *   1. initialise, if the env is selected for it: incomplete = all S bits, cur = S, cnt = 0
+ *   2. refresh (agent.py:151-171): if cur < S and count_cur(state) > cnt: clear bit cur, cur = S,
+ *      OC_TASKF_COMPLETED.  count_i is oc_progress's count_i
+ *   3. candidates C: every i < S with bit i set, kind != OC_SUB_NONE and doable_i; with
+ *      OC_TASK_DISTINCT also i != the cur of every scripted agent m' < m as its step 4 of this call
+ *      left it.  doable_i and lb_i are what oc_subtask_bounds gives on this state for the row
+ *      {kind, num_agents 1, agent {a}, start_mask, goal_mask}
+ *   4. choose: with OC_TASK_COMMIT, cur < S and cur in C: keep cur.  Otherwise new = the i in C
+ *      with the smallest lb_i (f32 <, ties to the lowest i), or S when C is empty; if new != cur and
+ *      new < S: cnt = count_new(state); cur = new.  OC_TASKF_SWITCHED iff cur at exit differs from
+ *      cur at entry (the value after step 1)
+ * ------------------------------------------------------------------------------------- */
+#define OC_TASK_INIT     1   /* every env below B starts its episode: task state initialised first */
+#define OC_TASK_COMMIT   2   /* keep the current subtask while it is still a candidate */
+#define OC_TASK_DISTINCT 4   /* a subtask an earlier scripted agent holds after its own choice in this
+                                call is no candidate */
+#define OC_TASKF_COMPLETED 0x01  /* the current subtask's count rose: removed from the incomplete set */
+#define OC_TASKF_SWITCHED  0x02  /* cur at exit != cur at entry (entry = after initialisation) */
+#define OC_TASKF_REINIT    0x04  /* task state initialised in this call */
+#define OC_TASK_PLANES(S) (OC_PROGRESS_EVENT_PLANES(S) + 2)
+
+/*   state        : B states (oc_layout); DONE and ERR envs are processed as their stored state is
+ *   state_prev   : nullable.  The envs whose state_prev flags carry OC_FLAG_DONE are the ones the
+ *                  step that produced `state` auto-reset: their task state is initialised first
+ *                  (OC_TASKF_REINIT; oc_reset_random's convention).  OC_TASK_INIT initialises every
+ *                  env and wins over state_prev; with neither, nothing is initialised
+ *   subtasks     : host array of S = num_subtasks rows; only kind, start_mask and goal_mask are read
+ *                  (capi.progress_subtasks rows serve).  OC_SUB_NONE rows are never candidates
+ *   agents       : host array of M = num_scripted distinct agent indices, in the caller's order: the
+ *                  priority order of OC_TASK_DISTINCT
+ *                  1 <= M <= A, 1 <= S <= 63 (index S is the None row of a policy table),
+ *                  M * S <= OC_MAX_SUBTASKS (the staging of the planner tables)
+ *   tstate       : required, caller-owned, u8 [M][OC_TASK_PLANES(S)][pitch], read and written in
+ *                  place (each env's bytes are read before they are written).  With EP =
+ *                  OC_PROGRESS_EVENT_PLANES(S), the planes of scripted agent m:
+ *                    0 .. EP-1 : the incomplete set, bit b of plane c is subtask 8c + b (oc_progress's
+ *                                events numbering); bits >= S are zero
+ *                    EP        : cur, the subtask the agent follows, or S for None: oc_nav_policy's
+ *                                `alloc` for a table whose rows 0 .. S-1 are these subtasks for agent m
+ *                                and whose row S is None (capi.policy_subtasks(subtasks + [None], ..))
+ *                    EP + 1    : cnt, the goal-object count of cur when it was taken
+ *   bound        : nullable, f32 [M][pitch], 4-byte aligned: the chosen subtask's lower bound, +0.0f
+ *                  for None
+ *   info         : nullable, u8 [M][pitch], OC_TASKF_* bits
+ * Columns >= B of every buffer stay untouched.  Stream-ordered, no allocation, no synchronisation
+ * (hipGraph-capturable, as oc_step).  A bad M, S, agents or flags, a NULL state, subtasks, agents
+ * or tstate, a misaligned bound, or a host-only handle is OC_EINVAL; B = 0 is OK. */
+int oc_task_select(const oc_handle* h, const void* state, const void* state_prev, const oc_subtask* subtasks,
+                   int32_t num_subtasks, const uint8_t* agents, int32_t num_scripted, int32_t flags, uint8_t* tstate,
+                   float* bound, uint8_t* info, int64_t B, void* stream);
+
+/* The same on the host (what oc_cpu_step is to oc_step): HOST buffers, works on OC_DEVICE_HOST
+ * handles, the kernel's row function compiled for the host, threaded over env ranges (nthreads
+ * 0 = the host's hardware threads; at least 1,024 rows each).  It never touches the device;
+ * oc_task_select never calls it.  The two agree byte for byte. */
+int oc_cpu_task_select(const oc_handle* h, const void* state, const void* state_prev, const oc_subtask* subtasks,
+                       int32_t num_subtasks, const uint8_t* agents, int32_t num_scripted, int32_t flags,
+                       uint8_t* tstate, float* bound, uint8_t* info, int64_t B, int32_t nthreads);
+
 #ifdef __cplusplus
 }
 #endif
