@@ -1419,6 +1419,207 @@ __global__ __launch_bounds__(kBlock) void oc_task_kernel(RollArgs R, TaskArgs Q,
     }
 }
 
+// The posterior over a watched agent's subtask (oc_belief_update), a sibling of oc_policy_kernel:
+// a group of 8 lanes per (env, watched agent), the watched agent m = blockIdx.y (the watched agents
+// of an env do not depend on each other).  What the S one-agent hypotheses about one agent share
+// is built once per env: every lane builds the agent's Level-0 view, lane k < 5 tests candidate
+// k's legality and keeps its successor row (target + interact), and lane 5 keeps state_prev's own
+// row with the full-state view, so that the doable test of a hypothesis is the same bound call on
+// another row.  The hypotheses are then walked with a wave-uniform index over the table in LDS (the
+// block writes its watched agent into the staged rows once); one that no group of the wave has
+// live is skipped (wave_any).  Per hypothesis the candidate lanes evaluate q_successor (goal
+// count, else the lower bound), lane 5 the distance of the doable test, and the group takes
+// oc_policy_kernel's butterfly min and ascending-k sum.  A group's S + 1 beliefs sit in LDS between
+// their one load and their one store (hypothesis i by lane i % 8: 8 consecutive envs per wave and
+// plane); a run-time hypothesis index into registers would put them in scratch.
+struct BeliefArgs {
+    double beta, nap;
+    int32_t S, M, flags;
+    uint8_t agents[4];
+};
+// the kernel's static LDS: the subtask rows and a group's beliefs (17 KB; allow_dyn_lds counts it)
+constexpr int kBeliefStaticLds = (int)(OC_MAX_SUBTASKS * sizeof(ocro::Sub)) + (kBlock / 8) * OC_MAX_SUBTASKS * (int)sizeof(double);
+template <int A, int K, bool W, bool GD>
+__global__ __launch_bounds__(kBlock) void oc_belief_kernel(RollArgs R, BeliefArgs Q, const uint8_t* __restrict__ sprev,
+                                                           const uint8_t* __restrict__ taken,
+                                                           const uint8_t* __restrict__ events,
+                                                           const uint8_t* __restrict__ blob_g, double* __restrict__ belief,
+                                                           uint8_t* __restrict__ bstate, uint8_t* __restrict__ map,
+                                                           uint8_t* __restrict__ info) {
+    constexpr int G = 8;
+    extern __shared__ __attribute__((aligned(16))) uint32_t blob_w[];
+    __shared__ ocro::Sub subs[OC_MAX_SUBTASKS];
+    __shared__ double bl[kBlock / G][OC_MAX_SUBTASKS];  // a group's beliefs, hypothesis i at [i]
+    stage_roll_tables(R, blob_g, blob_w, subs);
+    const uint8_t* blob = (const uint8_t*)blob_w;
+    const int64_t P = R.pitch;
+    using PL = Planes<A, K, W>;
+    using Row = ocro::RowT<K, W>;
+    const int lane = (int)(threadIdx.x & (G - 1));
+    const int S = Q.S, HP = (S + 8) >> 3, EP = (S + 7) >> 3;
+    const int m = (int)blockIdx.y, a = Q.agents[m];
+    // this block's watched agent into the staged rows; row S (S <= 63): a's Level-0 configuration
+    for (int i = threadIdx.x; i <= S; i += kBlock) {
+        ocro::Sub d = i < S ? subs[i] : ocro::Sub{};
+        d.kind = i < S ? d.kind : 1;
+        d.n = 1;
+        d.agent[0] = d.agent[1] = (uint8_t)a;
+        d.level = 0;
+        subs[i] = d;
+    }
+    __syncthreads();
+    const uint64_t subm = (1ull << S) - 1ull, all = subm | 1ull << S;
+    double* bel = belief + (int64_t)m * (S + 1) * P;
+    uint8_t* bs = bstate + (int64_t)m * 2 * HP * P;
+    double* mine = bl[threadIdx.x / G];
+    uint64_t real = 1ull << S;  // the hypotheses a fresh distribution holds
+    for (int i = 0; i < S; ++i) real |= subs[i].kind != 0 ? 1ull << i : 0ull;
+    const int64_t ngroups = (int64_t)gridDim.x * (kBlock / G);
+    for (int64_t e = (int64_t)blockIdx.x * (kBlock / G) + threadIdx.x / G; e < R.B; e += ngroups) {
+        // group-uniform from here on, except where `lane` is named
+        const bool init = (Q.flags & OC_BELIEF_INIT) != 0 || (sprev[PL::F * P + e] & OC_FLAG_DONE) != 0;
+        uint64_t open = 0ull, live = 0ull, ev = 0ull;
+        if (!init) {
+            for (int c = 0; c < HP; ++c) {
+                open |= (uint64_t)bs[c * P + e] << (8 * c);
+                live |= (uint64_t)bs[(HP + c) * P + e] << (8 * c);
+            }
+            if (events != nullptr)
+                for (int c = 0; c < EP; ++c) ev |= (uint64_t)events[c * P + e] << (8 * c);
+        }
+        open &= all;
+        live &= all;
+        ev &= subm;
+        int fl = 0;
+        bool uniform = false;
+        if (init) {
+            open = real;
+            uniform = true;
+            fl = OC_BELF_REINIT;
+        } else if ((ev & open) != 0ull) {
+            open &= ~ev;
+            uniform = true;
+            fl = OC_BELF_RESET;
+        }
+        uint64_t dirty;      // the planes this call writes
+        double total = 1.0;  // step 6's total; the uniform paths store what they computed (v * 1.0)
+        if (uniform) {
+            live = open;
+            dirty = all;
+            const double u = 1.0 / (double)__popcll(live);
+            for (int i = lane; i <= S; i += G) mine[i] = (live >> i) & 1ull ? u : 0.0;
+        } else {
+            dirty = live;
+            for (int i = lane; i <= S; i += G) mine[i] = (live >> i) & 1ull ? bel[i * P + e] : 0.0;
+            wave_lds_sync();
+            const Row r0 = load_row<A, K, W>(sprev, P, e);
+            int t = taken[a * P + e];
+            t = t > ocro::kNoop ? ocro::kNoop : t;
+            using Ops = ocro::RowOps<A, K, W, true, GD>;
+            Ops ops(R.L, blob, GD ? blob_g + R.L.dist_off : blob + R.L.dist_off);  // distances: LDS (narrow), device memory (wide)
+            const uint32_t mv = ops.none_movable(r0, a);  // the None hypothesis' movable actions, full state
+            ops.ac = ops.kNoAc;
+            Row v = r0;
+            const bool raised0 = ops.level0(v, subs[S]);
+            const bool lg = lane < 5 && !raised0 && ops.single_legal(v, a, lane);
+            const bool rc = raised0 || !__shfl((int)lg, t, G);  // the reference raises (if a subtask stays live)
+            // the row this lane bounds: candidate k's successor on lane k, state_prev itself on lane 5
+            Row rb = v;
+            if (lg && !rc) ops.interact(rb, a, lane);
+            if (lane >= 5) {
+                rb = r0;
+                ops.ac = ops.kNoAc;
+            }
+            const double cost = lane != ocro::kNoop ? 1.0 + 0.1 : 1.0;
+            const bool worker = lane == 5 || (lg && !rc);
+            double p0, p1;  // the None closed form
+            bool noop_mode;
+            ops.none_probs(__builtin_popcount(mv), Q.beta, Q.nap, p0, p1, noop_mode);
+            const double ln = t == ocro::kNoop ? p0 : p1;
+            total = 0.0;
+            for (int i = 0; i < S; ++i) {
+                const bool li = ((live >> i) & 1ull) != 0ull;
+                if (!ocro::wave_any(li)) continue;  // wave-uniform
+                const ocro::Sub& s = subs[i];
+                const bool sub = s.kind != 0;
+                // lane 5: q_successor's bound-only form on state_prev itself; its `dist` is the
+                // doable test's distance (full_bound's, with the same full-state configuration)
+                const int count = lane < 5 ? ops.goal_objects(v, s) : Ops::kBoundOnly;
+                double q = 0.0;
+                float dist = 0.0f;
+                if (li && sub && worker) q = ops.q_successor(rb, s, count, cost, dist);
+                if (!li) continue;
+                const bool doable = !sub || __shfl((int)(dist < (float)R.L.perimeter), 5, G) != 0;
+                double bi = 0.0;
+                if (!doable) {
+                    live &= ~(1ull << i);
+                    fl |= OC_BELF_PRUNED;
+                } else {
+                    bi = mine[i];
+                    if (!rc) {
+                        double l = ln;
+                        if (sub) {
+                            double mq = lg ? q : 1.0e300;
+#pragma unroll
+                            for (int off = 1; off < G; off <<= 1) {
+                                const double o = __shfl_xor(mq, off, G);
+                                mq = o < mq ? o : mq;
+                            }
+                            const double w = lg ? exp(Q.beta * (mq - q)) : 0.0;
+                            double sum = 0.0;  // ascending k: the sequential sum
+                            for (int c = 0; c < 5; ++c) sum += __shfl(w, c, G);
+                            l = __shfl(w / sum, t, G);
+                        }
+                        bi = bi * l;
+                    }
+                    total += bi;
+                }
+                if (lane == 0) mine[i] = bi;
+            }
+            const bool raises = rc && (live & subm) != 0ull;
+            fl |= raises ? OC_BELF_RAISED : OC_BELF_UPDATED;
+            if ((live >> S) & 1ull) {
+                double bn = mine[S];
+                if (!raises) bn = bn * ln;
+                total += bn;
+                if (lane == 0) mine[S] = bn;
+            }
+        }
+        wave_lds_sync();
+        // step 6 on this lane's planes, their stores, and the lowest live hypothesis holding the maximum
+        const double r = total == 0.0 ? 1.0 / (double)__popcll(live) : 1.0 / total;
+        int best = S;
+        double bv = -1.0;
+        for (int i = lane; i <= S; i += G) {
+            double x = mine[i];
+            const bool li = ((live >> i) & 1ull) != 0ull;
+            if (li) x = total == 0.0 ? r : x * r;
+            if ((dirty >> i) & 1ull) bel[i * P + e] = x;
+            if (li && x > bv) {
+                best = i;
+                bv = x;
+            }
+        }
+#pragma unroll
+        for (int off = 1; off < G; off <<= 1) {
+            const double ov = __shfl_xor(bv, off, G);
+            const int oi = __shfl_xor(best, off, G);
+            const bool take = ov > bv || (ov == bv && oi < best);
+            bv = take ? ov : bv;
+            best = take ? oi : best;
+        }
+        if (lane == 0) {
+            for (int c = 0; c < HP; ++c) {
+                bs[c * P + e] = (uint8_t)(open >> (8 * c));
+                bs[(HP + c) * P + e] = (uint8_t)(live >> (8 * c));
+            }
+            if (map != nullptr) map[m * P + e] = (uint8_t)best;
+            if (info != nullptr) info[m * P + e] = (uint8_t)fl;
+        }
+        wave_lds_sync();  // the group's slots are free for its next env
+    }
+}
+
 // ---- wide levels (more than 255 cells: u16 cell ids) ----------------------------------------
 // A wide level (more than 255 cells, u16 cell ids) is stepped by ocsw::step4w: the SWAR step
 // with every cell-valued quantity as two byte words (its low and high bytes, the wide layout's
@@ -2361,8 +2562,10 @@ static int roll_args(const oc_handle* h, const oc_subtask* subtasks, int32_t num
 // by default (graphs of more than ~245 nodes) the kernel must be allowed more, up to the CU's
 // 160 KB; the kernel's static LDS counts against the same limit.
 constexpr int kLdsPerCu = 160 * 1024;
-static int allow_dyn_lds(const void* kernel, int dyn) {
-    if (dyn <= 48 * 1024) return OC_OK;
+static int allow_dyn_lds(const void* kernel, int dyn, int static_lds = 16 * 1024) {
+    // static_lds: an upper bound of the kernel's static LDS; together with `dyn` within the default
+    // 64 KB nothing needs to be set
+    if (dyn + static_lds <= 64 * 1024) return OC_OK;
     hipFuncAttributes fa;
     if (hipFuncGetAttributes(&fa, kernel) != hipSuccess) return hip_check("hipFuncGetAttributes");
     if ((int64_t)fa.sharedSizeBytes + dyn > kLdsPerCu)
@@ -3132,6 +3335,121 @@ int oc_cpu_task_select(const oc_handle* h, const void* state, const void* state_
                 ocro::RowOps<a(), k(), w(), false, true> ops(R.L, blob);
                 ops.task_env(load_row<a(), k(), w()>(sin, P, e), R.subs, Q.S, Q.M, Q.flags, init, tstate + e,
                              bound != nullptr ? bound + e : nullptr, info != nullptr ? info + e : nullptr, P);
+            }
+            return OC_OK;
+        });
+    });
+}
+
+// oc_belief_update / oc_cpu_belief_update: the arguments both check, and the call's RollArgs (the S
+// rows of the table as one-agent Level-0 configurations; the kernels set the watched agent) and
+// BeliefArgs
+static int belief_args(const oc_handle* h, const void* state_prev, const uint8_t* taken, const oc_subtask* subtasks,
+                       int32_t num_subtasks, const uint8_t* agents, int32_t num_watched, double beta, double nap,
+                       int32_t flags, const double* belief, const uint8_t* bstate, int64_t B, bool host, RollArgs& R,
+                       BeliefArgs& Q) {
+    if (subtasks == nullptr || agents == nullptr || belief == nullptr || bstate == nullptr)
+        return fail(OC_EINVAL, "belief_update: subtasks, agents, belief and bstate are required");
+    if (B < 0) return fail(OC_EINVAL, "belief_update: B %lld", (long long)B);
+    const int32_t S = num_subtasks, M = num_watched;
+    if (M < 1 || M > h->A) return fail(OC_EINVAL, "belief_update: num_watched %d (1..%d)", M, h->A);
+    if (S < 1 || S > 63) return fail(OC_EINVAL, "belief_update: num_subtasks %d (1..63)", S);
+    if (flags < 0 || flags > OC_BELIEF_INIT) return fail(OC_EINVAL, "belief_update: flags %d", flags);
+    if (!(flags & OC_BELIEF_INIT) && (state_prev == nullptr || taken == nullptr))
+        return fail(OC_EINVAL, "belief_update: state_prev and taken are required without OC_BELIEF_INIT");
+    if (!(beta == beta) || !(nap >= 0.0 && nap <= 1.0))
+        return fail(OC_EINVAL, "belief_update: beta %g, none_action_prob %g", beta, nap);
+    for (int m = 0; m < M; ++m) {
+        if (agents[m] >= h->A) return fail(OC_EINVAL, "belief_update: agent %d", agents[m]);
+        for (int q = 0; q < m; ++q)
+            if (agents[q] == agents[m]) return fail(OC_EINVAL, "belief_update: agent %d listed twice", agents[m]);
+    }
+    if (((uintptr_t)belief & 7u) || ((uintptr_t)state_prev & 1u)) return fail(OC_EINVAL, "belief_update: misaligned buffer");
+    oc_subtask rows[OC_MAX_SUBTASKS];
+    for (int i = 0; i < S; ++i) {
+        oc_subtask& d = rows[i];
+        d = oc_subtask{};
+        d.kind = subtasks[i].kind;
+        d.num_agents = 1;
+        d.agent[0] = 0;
+        d.start_mask[0] = subtasks[i].start_mask[0];
+        d.start_mask[1] = subtasks[i].start_mask[1];
+        d.goal_mask = subtasks[i].goal_mask;
+        d.level = OC_LEVEL0;
+    }
+    if (const int rc = roll_args(h, rows, S, B, R, false, host)) return rc;
+    Q.beta = beta;
+    Q.nap = nap;
+    Q.S = S;
+    Q.M = M;
+    Q.flags = flags;
+    for (int m = 0; m < 4; ++m) Q.agents[m] = m < M ? agents[m] : 0;
+    return OC_OK;
+}
+
+int oc_belief_update(const oc_handle* h, const void* state_prev, const uint8_t* taken, const uint8_t* events,
+                     const oc_subtask* subtasks, int32_t num_subtasks, const uint8_t* agents, int32_t num_watched,
+                     double beta, double none_action_prob, int32_t flags, double* belief, uint8_t* bstate, uint8_t* map,
+                     uint8_t* info, int64_t B, void* stream) {
+    if (h == nullptr) return fail(OC_EINVAL, "bad argument");
+    ErrScope es_(h);
+    OC_NEED_DEVICE(h);
+    RollArgs R;
+    BeliefArgs Q;
+    if (const int rc = belief_args(h, state_prev, taken, subtasks, num_subtasks, agents, num_watched, beta,
+                                   none_action_prob, flags, belief, bstate, B, false, R, Q))
+        return rc;
+    if (B == 0) return OC_OK;
+    // oc_nav_policy's grid for 8-lane groups, once per watched agent
+    const int64_t rows_per_block = kBlock / 8;
+    const int64_t need = (B + rows_per_block - 1) / rows_per_block, cap = (int64_t)h->cus * 8;
+    const dim3 grid((unsigned)(need < cap ? need : cap), (unsigned)Q.M);
+    hipStream_t st = (hipStream_t)stream;
+    return dispatch_plan(h, [&](auto a, auto k, auto w, auto gd) {
+        const auto kernel = oc_belief_kernel<a(), k(), w(), gd()>;
+        if (const int rc = allow_dyn_lds((const void*)kernel, R.blob_words * 4, kBeliefStaticLds)) return rc;
+        hipLaunchKernelGGL(kernel, grid, dim3(kBlock), R.blob_words * 4, st, R, Q, (const uint8_t*)state_prev, taken,
+                           events, h->roll_blob, belief, bstate, map, info);
+        return hip_check("oc_belief_update launch");
+    });
+}
+
+int oc_cpu_belief_update(const oc_handle* h, const void* state_prev, const uint8_t* taken, const uint8_t* events,
+                         const oc_subtask* subtasks, int32_t num_subtasks, const uint8_t* agents, int32_t num_watched,
+                         double beta, double none_action_prob, int32_t flags, double* belief, uint8_t* bstate,
+                         uint8_t* map, uint8_t* info, int64_t B, int32_t nthreads) {
+    if (h == nullptr || nthreads < 0) return fail(OC_EINVAL, "bad argument");
+    ErrScope es_(h);
+    RollArgs R;
+    BeliefArgs Q;
+    if (const int rc = belief_args(h, state_prev, taken, subtasks, num_subtasks, agents, num_watched, beta,
+                                   none_action_prob, flags, belief, bstate, B, true, R, Q))
+        return rc;
+    if (B == 0) return OC_OK;
+    const int64_t nt = host_threads(nthreads, B, 1024);  // >= 1,024 rows (M x S hypotheses each) per thread
+    const uint8_t* blob = h->roll_blob_host.data();
+    const uint8_t* sprev = (const uint8_t*)state_prev;
+    return run_ranges(nt, [&](int64_t i) {
+        const int64_t e0 = B * i / nt, e1 = B * (i + 1) / nt;
+        return dispatch_w(h, [&](auto a, auto k, auto w) {
+            using PL = Planes<a(), k(), w()>;
+            using Row = ocro::RowT<k(), w()>;
+            const int64_t P = R.pitch;
+            const int S = Q.S, HP = (S + 8) >> 3, EP = (S + 7) >> 3;
+            for (int64_t e = e0; e < e1; ++e) {
+                const bool init = (Q.flags & OC_BELIEF_INIT) != 0 || (sprev[PL::F * P + e] & OC_FLAG_DONE) != 0;
+                uint64_t ev = 0ull;
+                if (!init && events != nullptr)
+                    for (int c = 0; c < EP; ++c) ev |= (uint64_t)events[c * P + e] << (8 * c);
+                const Row r0 = init ? Row{} : load_row<a(), k(), w()>(sprev, P, e);
+                for (int m = 0; m < Q.M; ++m) {
+                    const int ag = Q.agents[m];
+                    ocro::RowOps<a(), k(), w(), true, true> ops(R.L, blob);
+                    ops.belief_env(r0, R.subs, S, ag, init ? ocro::kNoop : (int)taken[ag * P + e], ev, init, Q.beta, Q.nap,
+                                   belief + (int64_t)m * (S + 1) * P + e, bstate + (int64_t)m * 2 * HP * P + e,
+                                   map != nullptr ? map + m * P + e : nullptr, info != nullptr ? info + m * P + e : nullptr,
+                                   P);
+                }
             }
             return OC_OK;
         });

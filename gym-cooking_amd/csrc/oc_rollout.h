@@ -1167,10 +1167,29 @@ struct RowOps {
         double cost = 1.0;
         if (c0 != kNoop) cost += 0.1;
         if (s.n == 2 && c1 != kNoop) cost += 0.1;
-        double v = 0.0;
-        if (!(goal_objects(r, s) > count)) v = (double)lower_bound(r, s) * (1.0 + 0.1) - 1.09;
-        q = cost + 1.0 * v;
+        float dist;
+        q = q_successor(r, s, count, cost, dist);
         return true;
+    }
+    // The half of q_value_count that depends on the subtask: from a successor row, the count its
+    // goal test compares with and the action's cost to Q (value_init's value of the successor,
+    // e2e_brtdp.py:678-729).  `dist` becomes the bound's distance part (World.get_lower_bound_
+    // between, without the holding penalty), +0.0f where the goal test passes.  oc_belief_update
+    // evaluates it once per (hypothesis, successor) on successors it builds once per env.
+    // count = kBoundOnly: no goal test passes, so the bound is always walked and `dist` is the
+    // distance subtask_alloc_is_doable compares with the perimeter (full_bound's, when this object
+    // holds full_bound's configuration: no Level-0 view, the subtask agent active): the belief
+    // kernel's doable lane.
+    static constexpr int kBoundOnly = 0x7FFFFFFF;
+    OC_RH double q_successor(const Row& r, const Sub& s, int count, double cost, float& dist) const {
+        double v = 0.0;
+        dist = 0.0f;
+        if (!(goal_objects(r, s) > count)) {
+            float pen;
+            dist = lower_bound_parts<false>(bound_row<false>(r), r, s, pen);
+            v = (double)(dist + pen) * (1.0 + 0.1) - 1.09;
+        }
+        return cost + 1.0 * v;
     }
 
     // BayesianDelegator.prob_nav_actions(..., no_level_1=True) (bayesian_delegator.py:461-689).
@@ -1403,6 +1422,140 @@ struct RowOps {
             if (bound != nullptr) bound[m * P] = cur < S ? best : 0.0f;
             if (info != nullptr) info[m * P] = (uint8_t)fl;
         }
+    }
+
+    // ---- oc_belief_update: the posterior over a watched agent's subtask ----------------------
+    // One (env, watched agent a) of oc_belief_update (include/oc_engine.h, "The rule"), the whole
+    // row on one lane: the host call's row (the kernel spreads the same steps over a lane group).
+    // subs: the S rows of the table (kind, start, goal are read; the agent is a).  r0 = state_prev's
+    // row (unread when init), taken = a's executed action, ev = the step's events (0 = none given).
+    // belief / bs / map / info point at column e of the watched agent's planes, P apart.
+    //   set_priors / SubtaskAllocDistribution.__init__      utils/agent.py:185-192, utils.py:160-175
+    //   subtask_alloc_is_doable -> delete                   bayesian_delegator.py:1040-1050
+    //   prob_nav_actions -> update                          bayesian_delegator.py:1052-1068
+    //   normalize                                           utils.py:186-193
+    OC_RH void belief_env(const Row& r0, const Sub* subs, int S, int a, int taken, uint64_t ev, bool init, double beta,
+                          double nap, double* belief, uint8_t* bs, uint8_t* map, uint8_t* info, int64_t P) {
+        const int HP = (S + 8) >> 3;
+        const uint64_t subm = (1ull << S) - 1ull, all = subm | 1ull << S;
+        uint64_t open = 0ull, live = 0ull;
+        for (int c = 0; c < HP; ++c) {
+            open |= (uint64_t)bs[c * P] << (8 * c);
+            live |= (uint64_t)bs[(HP + c) * P] << (8 * c);
+        }
+        open &= all;
+        live &= all;
+        int fl = 0;
+        bool uniform = false;
+        if (init) {
+            open = 1ull << S;
+            for (int i = 0; i < S; ++i) open |= subs[i].kind != 0 ? 1ull << i : 0ull;
+            uniform = true;
+            fl = 4;  // OC_BELF_REINIT
+        } else if ((ev & subm & open) != 0ull) {
+            open &= ~(ev & subm);
+            uniform = true;
+            fl = 8;  // OC_BELF_RESET
+        }
+        if (uniform) {
+            live = open;
+            const double u = 1.0 / (double)__builtin_popcountll(live);
+            for (int i = 0; i <= S; ++i) belief[i * P] = (live >> i) & 1ull ? u : 0.0;
+        } else {
+            const int t = taken > kNoop ? kNoop : taken;
+            auto row_of = [&](int i) OC_RL {
+                Sub s = subs[i];
+                s.n = 1;
+                s.agent[0] = s.agent[1] = (uint8_t)a;
+                s.level = 0;
+                return s;
+            };
+            // 3. prune: oc_subtask_bounds' doable byte on the full state
+            const BoundRow br = bound_row<true>(r0);
+            for (int i = 0; i < S; ++i) {
+                if (!((live >> i) & 1ull)) continue;
+                float lb;
+                if (full_bound(br, r0, row_of(i), lb)) continue;
+                live &= ~(1ull << i);
+                belief[i * P] = 0.0;
+                fl |= 2;  // OC_BELF_PRUNED
+            }
+            const bool any_sub = (live & subm) != 0ull;
+            // 4. the raise test on a's Level-0 view (the same for every one-agent hypothesis)
+            const uint32_t mv = none_movable(r0, a);  // the None hypothesis' full-state movable actions
+            ac = kNoAc;
+            Row v = r0;
+            Sub sa{};
+            sa.kind = 1;
+            sa.n = 1;
+            sa.agent[0] = sa.agent[1] = (uint8_t)a;
+            bool raises = level0(v, sa);
+            uint32_t legal = 0u;
+            if (!raises)
+                for (int k = 0; k < 5; ++k) legal |= single_legal(v, a, k) ? 1u << k : 0u;
+            raises = any_sub && (raises || !((legal >> t) & 1u));
+            if (raises) {
+                fl |= 16;  // OC_BELF_RAISED
+            } else {
+                fl |= 1;  // OC_BELF_UPDATED
+                // 5. multiply: the successors once per env, the goal test and bound per hypothesis
+                Row succ[5];
+                if (any_sub)
+                    for (int k = 0; k < 5; ++k) {
+                        succ[k] = v;
+                        if ((legal >> k) & 1u) interact(succ[k], a, k);
+                    }
+                double p0, p1;
+                bool noop_mode;
+                none_probs(__builtin_popcount(mv), beta, nap, p0, p1, noop_mode);
+                const double ln = t == kNoop ? p0 : p1;
+                for (int i = 0; i <= S; ++i) {
+                    if (!((live >> i) & 1ull)) continue;
+                    double l = ln;
+                    if (i < S && subs[i].kind != 0) {
+                        const Sub s = row_of(i);
+                        const int count = goal_objects(v, s);
+                        double q[5], m = 1.0e300;
+                        for (int k = 0; k < 5; ++k) {
+                            if (!((legal >> k) & 1u)) continue;
+                            float dist;
+                            q[k] = q_successor(succ[k], s, count, k != kNoop ? 1.0 + 0.1 : 1.0, dist);
+                            m = q[k] < m ? q[k] : m;
+                        }
+                        double sum = 0.0, wt = 0.0;
+                        for (int k = 0; k < 5; ++k) {
+                            if (!((legal >> k) & 1u)) continue;
+                            const double w = exp(beta * (m - q[k]));
+                            sum += w;
+                            if (k == t) wt = w;
+                        }
+                        l = wt / sum;
+                    }
+                    belief[i * P] = belief[i * P] * l;
+                }
+            }
+            // 6. normalise
+            double total = 0.0;
+            for (int i = 0; i <= S; ++i)
+                if ((live >> i) & 1ull) total += belief[i * P];
+            const double r = total == 0.0 ? 1.0 / (double)__builtin_popcountll(live) : 1.0 / total;
+            for (int i = 0; i <= S; ++i)
+                if ((live >> i) & 1ull) belief[i * P] = total == 0.0 ? r : belief[i * P] * r;
+        }
+        // 7. the lowest live hypothesis holding the maximum
+        int best = S;
+        double bv = -1.0;
+        for (int i = 0; i <= S; ++i)
+            if (((live >> i) & 1ull) && belief[i * P] > bv) {
+                best = i;
+                bv = belief[i * P];
+            }
+        for (int c = 0; c < HP; ++c) {
+            bs[c * P] = (uint8_t)(open >> (8 * c));
+            bs[(HP + c) * P] = (uint8_t)(live >> (8 * c));
+        }
+        if (map != nullptr) *map = (uint8_t)best;
+        if (info != nullptr) *info = (uint8_t)fl;
     }
 };
 

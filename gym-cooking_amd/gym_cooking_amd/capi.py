@@ -40,7 +40,12 @@ EXPORTED_SYMBOLS = (
     "oc_set_likelihood_form", "oc_observe", "oc_cpu_observe", "oc_progress", "oc_cpu_progress",
     "oc_set_start_cells", "oc_get_start_cells", "oc_reset_random", "oc_cpu_reset_random",
     "oc_nav_policy", "oc_cpu_nav_policy", "oc_task_select", "oc_cpu_task_select",
+    "oc_belief_update", "oc_cpu_belief_update",
 )
+
+# oc_belief_update: the call flag, and the per-(env, watched agent) info bits
+OC_BELIEF_INIT = 1
+BELF_UPDATED, BELF_PRUNED, BELF_REINIT, BELF_RESET, BELF_RAISED = 0x01, 0x02, 0x04, 0x08, 0x10
 
 # oc_task_select: call flags, and the per-agent info bits
 OC_TASK_INIT, OC_TASK_COMMIT, OC_TASK_DISTINCT = 1, 2, 4
@@ -75,6 +80,13 @@ def task_planes(S: int) -> int:
     """Byte planes of one scripted agent's oc_task_select state for S subtasks (OC_TASK_PLANES):
     the incomplete set (event_planes(S) planes), then cur, then cnt."""
     return event_planes(S) + 2
+
+
+def belief_planes(S: int) -> int:
+    """HP of oc_belief_update for S subtasks (OC_BELIEF_PLANES): byte planes of one bit set over the
+    S + 1 hypotheses (bit b of plane c is hypothesis 8c + b, hypothesis S is None).  A watched
+    agent's bstate is 2 * HP planes (open, then live)."""
+    return (S + 8) // 8
 
 
 class OcLevelDesc(ctypes.Structure):
@@ -305,6 +317,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.oc_task_select.argtypes = [vp, vp, vp, ctypes.POINTER(OcSubtask), i32, vp, i32, i32, vp, vp, vp, i64, vp]
     lib.oc_cpu_task_select.restype = ctypes.c_int
     lib.oc_cpu_task_select.argtypes = [vp, vp, vp, ctypes.POINTER(OcSubtask), i32, vp, i32, i32, vp, vp, vp, i64, i32]
+    lib.oc_belief_update.restype = ctypes.c_int
+    lib.oc_belief_update.argtypes = [vp, vp, vp, vp, ctypes.POINTER(OcSubtask), i32, vp, i32, ctypes.c_double,
+                                     ctypes.c_double, i32, vp, vp, vp, vp, i64, vp]
+    lib.oc_cpu_belief_update.restype = ctypes.c_int
+    lib.oc_cpu_belief_update.argtypes = [vp, vp, vp, vp, ctypes.POINTER(OcSubtask), i32, vp, i32, ctypes.c_double,
+                                         ctypes.c_double, i32, vp, vp, vp, vp, i64, i32]
     lib.oc_cpu_step.restype = ctypes.c_int
     lib.oc_cpu_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i32]
     lib.oc_step_n.restype = ctypes.c_int

@@ -367,6 +367,55 @@ class OvercookedBatch(_StartCells):
                 _ptr(bound), _ptr(info), self.B, self._stream())
         return _bound(self.lib.oc_task_select, args)
 
+    def new_belief_state(self, S: int, M: int):
+        """Buffers of oc_belief_update for M watched agents over S subtasks, zeroed: (belief f64
+        [M, S + 1, pitch], bstate u8 [M, 2 * capi.belief_planes(S), pitch], map u8 [M, pitch], info
+        u8 [M, pitch]).  The first call on them passes capi.OC_BELIEF_INIT."""
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.device)  # noqa: E731
+        return (z((M, S + 1, self.pitch), torch.float64), z((M, 2 * capi.belief_planes(S), self.pitch), torch.uint8),
+                z((M, self.pitch), torch.uint8), z((M, self.pitch), torch.uint8))
+
+    def belief_update(self, prev: Optional[torch.Tensor], taken: Optional[torch.Tensor], subtasks, agents,
+                      belief: torch.Tensor, bstate: torch.Tensor, events: Optional[torch.Tensor] = None,
+                      beta: float = 1.3, none_action_prob: float = 0.5, flags: int = 0,
+                      map: Optional[torch.Tensor] = None, info: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The posterior over each watched agent's subtask (oc_belief_update), updated in place over
+        one step: `prev` the states the step left, `taken` its executed actions (step's exec_out),
+        `events` oc_progress's events of that step (or None: no prior reset).  Hypothesis i < S is
+        "the agent alone follows subtasks[i]", hypothesis S is None; `belief`, `bstate`, `map` come
+        from new_belief_state.  capi.OC_BELIEF_INIT in `flags` starts every env over (prev, taken
+        and events may then be None); the envs whose `prev` flags carry DONE start over by
+        themselves.  Not idempotent: every call multiplies the step's likelihoods in.  Returns
+        info u8 [M, pitch] (capi.BELF_*)."""
+        if info is None:
+            info = torch.empty((len(agents), self.pitch), dtype=torch.uint8, device=self.device)
+        self.belief_update_launcher(prev, taken, subtasks, agents, belief, bstate, events, beta, none_action_prob,
+                                    flags, map, info)()
+        return info
+
+    def belief_update_launcher(self, prev: Optional[torch.Tensor], taken: Optional[torch.Tensor], subtasks, agents,
+                               belief: torch.Tensor, bstate: torch.Tensor, events: Optional[torch.Tensor], beta: float,
+                               none_action_prob: float, flags: int, map: Optional[torch.Tensor],
+                               info: Optional[torch.Tensor]):
+        """An oc_belief_update call bound once (see rollout_launcher)."""
+        S, M = len(subtasks), len(agents)
+        if prev is not None:
+            self._check(prev, self.layout.state_bytes)
+        if taken is not None:
+            self._check(taken, self.A * self.pitch)
+        if events is not None:
+            self._check(events, capi.event_planes(S) * self.pitch)
+        self._check(belief, 8 * M * (S + 1) * self.pitch, (torch.float64,))
+        self._check(bstate, M * 2 * capi.belief_planes(S) * self.pitch)
+        for t in (map, info):
+            if t is not None:
+                self._check(t, M * self.pitch)
+        ags = (ctypes.c_uint8 * M)(*[int(a) for a in agents])
+        args = (self._h, _ptr(prev), _ptr(taken), _ptr(events), capi.subtask_array(subtasks), S, ags, M, float(beta),
+                float(none_action_prob), int(flags), _ptr(belief), _ptr(bstate), _ptr(map), _ptr(info), self.B,
+                self._stream())
+        return _bound(self.lib.oc_belief_update, args)
+
     def subtask_bounds(self, state: torch.Tensor, subtasks, lower_bound: Optional[torch.Tensor] = None,
                        doable: Optional[torch.Tensor] = None):
         """Full-state subtask bounds (oc_subtask_bounds): for every env and configuration,
@@ -639,6 +688,36 @@ class CpuStepper(_StartCells):
         ags = (ctypes.c_uint8 * M)(*[int(a) for a in agents])
         capi.check(self.lib.oc_cpu_task_select(self._h, p(state), p(prev), capi.subtask_array(subtasks), S, ags, M,
                                                int(flags), p(tstate), p(bound), p(info), B, self.nthreads))
+        return info
+
+    def new_belief_state(self, S: int, M: int):
+        """Host buffers of oc_cpu_belief_update, zeroed; mirrors OvercookedBatch.new_belief_state."""
+        P = self.pitch
+        return (np.zeros((M, S + 1, P), np.float64), np.zeros((M, 2 * capi.belief_planes(S), P), np.uint8),
+                np.zeros((M, P), np.uint8), np.zeros((M, P), np.uint8))
+
+    def belief_update(self, prev: Optional[np.ndarray], taken: Optional[np.ndarray], subtasks, agents,
+                      belief: np.ndarray, bstate: np.ndarray, events: Optional[np.ndarray] = None, beta: float = 1.3,
+                      none_action_prob: float = 0.5, flags: int = 0, map: Optional[np.ndarray] = None,
+                      info: Optional[np.ndarray] = None) -> np.ndarray:
+        """oc_cpu_belief_update: the posterior over each watched agent's subtask in the host buffers;
+        mirrors OvercookedBatch.belief_update.  `belief` f64 [M, S + 1, pitch] and `bstate` u8
+        [M, 2 * capi.belief_planes(S), pitch] are updated in place; only columns below B are written
+        (buffers may end at column B of their last plane).  Returns info u8 [M, pitch]."""
+        S, M, B, P = len(subtasks), len(agents), self.B, self.pitch
+        info = np.zeros((M, P), np.uint8) if info is None else info
+        for a, n, dt in ((prev, self.layout.state_bytes, np.uint8), (taken, (self.A - 1) * P + B, np.uint8),
+                         (events, (capi.event_planes(S) - 1) * P + B, np.uint8),
+                         (belief, 8 * ((M * (S + 1) - 1) * P + B), np.float64),
+                         (bstate, (M * 2 * capi.belief_planes(S) - 1) * P + B, np.uint8),
+                         (map, (M - 1) * P + B, np.uint8), (info, (M - 1) * P + B, np.uint8)):
+            if a is not None and (a.dtype != dt or not a.flags.c_contiguous or a.nbytes < n):
+                raise ValueError("host buffers: contiguous %s of at least %d bytes" % (np.dtype(dt), n))
+        p = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        ags = (ctypes.c_uint8 * M)(*[int(a) for a in agents])
+        capi.check(self.lib.oc_cpu_belief_update(self._h, p(prev), p(taken), p(events), capi.subtask_array(subtasks), S,
+                                                 ags, M, float(beta), float(none_action_prob), int(flags), p(belief),
+                                                 p(bstate), p(map), p(info), B, self.nthreads))
         return info
 
     def progress(self, state_prev: np.ndarray, states: np.ndarray, subtasks, weights=None, n: int = 1,

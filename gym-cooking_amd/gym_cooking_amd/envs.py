@@ -844,6 +844,7 @@ class OvercookedVecEnv:
             self.batch.reset_random(self.state, None, self.seed, self._round, self.random_starts)
         self._stepped = False
         self._task_round = None  # partner_tasks(): the next call starts every env over
+        self._belief_round = None  # partner_beliefs(): likewise
         return self.state
 
     def step(self, actions: torch.Tensor):
@@ -959,6 +960,45 @@ class OvercookedVecEnv:
         self.batch.task_select(self.state, self._sub_rows, agents, self._task, prev, flags, None, self._task_info)
         B = self.num_envs
         return self._task[:, EP, :B], self._task_info[:, :B]
+
+    def partner_beliefs(self, agents, beta: float = 1.3, none_action_prob: float = 0.5, use_events: bool = True):
+        """What each watched agent of `agents` is doing, inferred from what it did
+        (oc_belief_update over ``subtasks``): per env and watched agent the reference's Bayesian
+        update of a posterior over "the agent alone follows subtask i" and None, over the last
+        step(): hypotheses that are no longer doable leave, the others are multiplied by the
+        Boltzmann likelihood (`beta`, `none_action_prob`) of the action the agent executed, and the
+        result is normalised.  With `use_events` an oc_progress launch over the same step supplies
+        the completion events, after which the priors start over uniform on the open subtasks.  The
+        belief lives in this env across step(): the first call after reset() (or with other agents)
+        initialises every env, a call after a step updates over that step (only the last one: call
+        once per step) and starts over the envs it auto-reset, and a second call on the same states
+        changes nothing.  Opt-in: step() does not compute it.  Returns (belief f64 [M, S + 1, B],
+        hypothesis S being None; map u8 [M, B], the most likely hypothesis; info u8 [M, B] of
+        capi.BELF_*), views of this env's buffers."""
+        agents = tuple(int(a) for a in agents)
+        S = len(self.subtasks)
+        if S == 0:
+            raise ValueError("the level's recipes have no subtasks")
+        M, B = len(agents), self.num_envs
+        if getattr(self, "_belief_agents", None) != agents:
+            self._belief_agents = agents
+            self._belief = self.batch.new_belief_state(S, M)
+            self._belief_events = torch.zeros((1, capi.event_planes(S), self.P), dtype=torch.uint8,
+                                              device=self.batch.device)
+            self._belief_round = None
+        bel, bst, bmap, info = self._belief
+        if getattr(self, "_belief_round", None) is None:
+            self.batch.belief_update(None, None, self._sub_rows, agents, bel, bst, None, beta, none_action_prob,
+                                     capi.OC_BELIEF_INIT, bmap, info)
+        elif self._belief_round != self._round:  # stepped since: the other buffer is the state before
+            prev, events = self._s[self._i ^ 1], None
+            if use_events:
+                events = self._belief_events
+                self.batch.progress(prev, self.state, self._sub_rows, None, 1, None, events, None)
+            self.batch.belief_update(prev, self.ex, self._sub_rows, agents, bel, bst, events, beta, none_action_prob,
+                                     0, bmap, info)
+        self._belief_round = self._round
+        return bel[:, :, :B], bmap[:, :B], info[:, :B]
 
     def scripted_actions(self, agents, beta: float = 1.3,
                          mode: int = capi.OC_POLICY_SAMPLE | capi.OC_POLICY_COUNT_STATE,

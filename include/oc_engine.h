@@ -785,6 +785,98 @@ int oc_cpu_task_select(const oc_handle* h, const void* state, const void* state_
                        int32_t num_subtasks, const uint8_t* agents, int32_t num_scripted, int32_t flags,
                        uint8_t* tstate, float* bound, uint8_t* info, int64_t B, int32_t nthreads);
 
+/* ---------------------------------------------------------------------------------------
+ * Per-env Bayesian belief over a watched agent's subtask (additive to ABI 12): Bayesian Delegation's
+ * inference step on the batch.  Per env and watched agent a, a posterior over S + 1 hypotheses:
+ * hypothesis i < S is "a alone follows subtasks[i]", hypothesis S is "a follows None".
+ *   update_subtasks (set_priors in place of bayes_update after a completion)
+ *                                   gym_cooking/utils/agent.py:176-203
+ *   bayes_update                    delegation_planner/bayesian_delegator.py:1026-1072
+ *   subtask_alloc_is_doable         bayesian_delegator.py:98-156
+ *   prob_nav_actions (no_level_1)   bayesian_delegator.py:461-689 (the assert at :672)
+ *   SubtaskAllocDistribution.__init__, delete, update, normalize, get_max
+ *                                   delegation_planner/utils.py:160-215 (normalize :186-193)
+ * Build-defined, like oc_task_select: one-agent hypotheses about one agent, uniform priors only
+ * (the reference enumerates joint allocations and offers spatial priors), fresh-planner Q values
+ * (oc_nav_policy's), and ties of the maximum go to the lowest index (get_max draws at random).
+ *
+ * With HP = OC_BELIEF_PLANES(S) = ceil((S + 1) / 8), the state of a watched agent is two bit sets
+ * over the hypotheses, bit b of plane c being hypothesis 8c + b, bits > S zero:
+ *   open : the subtasks nobody has completed this episode (and bit S)
+ *   live : the hypotheses still in the distribution
+ * The rule, for env e and watched agent a = agents[m]:
+ *   1. initialise, with OC_BELIEF_INIT or when state_prev's flags carry OC_FLAG_DONE (the step
+ *      auto-reset the env: oc_task_select's convention): open = every i < S whose kind is not
+ *      OC_SUB_NONE, and bit S; live = open; every live belief = 1.0 / n_live (n_live = the number
+ *      of live hypotheses), the others +0.0 (SubtaskAllocDistribution.__init__).  OC_BELF_REINIT;
+ *      go to 7.
+ *   2. reset priors, if events is given and events & open is non-zero (an open subtask was
+ *      completed; agent.py:185-192 calls set_priors instead of bayes_update): open &= ~events;
+ *      live = open; the beliefs uniform as in 1.  OC_BELF_RESET; go to 7.
+ *   3. prune: a live i < S whose row {kind_i, num_agents 1, agent {a}, start_mask_i, goal_mask_i}
+ *      is not doable on state_prev (exactly oc_subtask_bounds' doable byte) leaves live and its
+ *      belief becomes +0.0.  OC_BELF_PRUNED.
+ *   4. raise test, only if some i < S is still live: prob_nav_actions raises if the Level-0
+ *      configuration for {a} raises (two other agents on one square, OC_POL_RAISES' first case) or
+ *      if a's taken action is not in get_actions on that Level-0 view (the assert at :672); for
+ *      one-agent hypotheses neither depends on i.  Then OC_BELF_RAISED, step 5 is skipped.
+ *   5. multiply: for the live i ascending, belief_i = belief_i * L_i (one f64 multiply).  For
+ *      i < S, L_i = p_taken of exactly the distribution oc_nav_policy defines for the row
+ *      (state_prev[e], subtask i for agent a) with OC_POLICY_COUNT_STATE: m = min Q,
+ *      w_k = exp(beta * (m - Q_k)), the sum ascending from +0.0, p = w / sum; the reference's
+ *      softmax(beta * (Q_taken - Q_k))[taken] on a fresh planner configured on obs_tm1.  L_S is
+ *      oc_nav_policy's None closed form: n = a's movable actions in the full state, L_S =
+ *      p(no-op) if the taken action is the no-op, else p(each movable action); n = 0: 1 and 0.  (A
+ *      live OC_SUB_NONE row inside the table takes L_S.)  OC_BELF_UPDATED.
+ *   6. normalise (utils.py:186-193): total = +0.0 plus the live beliefs in ascending order; if
+ *      total == 0 every live belief = 1.0 / n_live, else r = 1.0 / total and belief_i =
+ *      belief_i * r (a multiply by the reciprocal, not a division).
+ *   7. map = the lowest live i holding the maximum belief.
+ * A second call without a step in between is not idempotent: it multiplies again.
+ * ------------------------------------------------------------------------------------- */
+#define OC_BELIEF_INIT 1         /* every env below B starts its episode: step 1 for all of them */
+#define OC_BELF_UPDATED 0x01     /* step 5 ran */
+#define OC_BELF_PRUNED  0x02     /* a hypothesis left the distribution in step 3 */
+#define OC_BELF_REINIT  0x04     /* initialised in this call (step 1) */
+#define OC_BELF_RESET   0x08     /* uniform priors over the open subtasks after a completion (step 2) */
+#define OC_BELF_RAISED  0x10     /* the reference's likelihood raises: pruned and normalised only */
+#define OC_BELIEF_PLANES(S) (((S) + 8) / 8)
+
+/*   state_prev   : B states (oc_layout), the states the step left (oc_step's state_in)
+ *   taken        : u8 [A][pitch], the executed actions of that step (oc_step's exec); codes > 4
+ *                  act as the no-op
+ *   events       : nullable, u8 [OC_PROGRESS_EVENT_PLANES(S)][pitch], oc_progress's events of that
+ *                  same step over the same S rows
+ *                  With OC_BELIEF_INIT state_prev, taken and events may be NULL (and are not read)
+ *   subtasks     : host array of S = num_subtasks rows, 1 <= S <= 63; only kind, start_mask and
+ *                  goal_mask are read (capi.progress_subtasks / policy_subtasks rows serve)
+ *   agents       : host array of M = num_watched distinct agent indices, 1 <= M <= A; the watched
+ *                  agents do not depend on each other
+ *   beta, none_action_prob : as oc_nav_policy (none_action_prob in [0, 1])
+ *   belief       : required, f64 [M][S + 1][pitch], 8-byte aligned, read and written in place
+ *   bstate       : required, u8 [M][2 * HP][pitch], read and written in place: planes 0 .. HP-1
+ *                  open, HP .. 2HP-1 live
+ *   map          : nullable, u8 [M][pitch]
+ *   info         : nullable, u8 [M][pitch], OC_BELF_* bits
+ * Columns >= B of every buffer stay untouched; a belief plane is written only where step 1 or 2
+ * ran or the hypothesis was live at entry.  Stream-ordered, no allocation, no synchronisation
+ * (hipGraph-capturable, as oc_step).  Bad arguments and a host-only handle are OC_EINVAL; B = 0
+ * is OK. */
+int oc_belief_update(const oc_handle* h, const void* state_prev, const uint8_t* taken, const uint8_t* events,
+                     const oc_subtask* subtasks, int32_t num_subtasks, const uint8_t* agents, int32_t num_watched,
+                     double beta, double none_action_prob, int32_t flags, double* belief, uint8_t* bstate, uint8_t* map,
+                     uint8_t* info, int64_t B, void* stream);
+
+/* The same on the host (what oc_cpu_step is to oc_step): HOST buffers, works on OC_DEVICE_HOST
+ * handles, the whole rule per (env, watched agent) as one scalar row function, threaded over env
+ * ranges (nthreads 0 = the host's hardware threads; at least 1,024 rows each).  It never touches
+ * the device; oc_belief_update never calls it.  The two agree on bstate, info and, up to the last
+ * bits of exp and of a fused multiply-add, on belief. */
+int oc_cpu_belief_update(const oc_handle* h, const void* state_prev, const uint8_t* taken, const uint8_t* events,
+                         const oc_subtask* subtasks, int32_t num_subtasks, const uint8_t* agents, int32_t num_watched,
+                         double beta, double none_action_prob, int32_t flags, double* belief, uint8_t* bstate,
+                         uint8_t* map, uint8_t* info, int64_t B, int32_t nthreads);
+
 #ifdef __cplusplus
 }
 #endif
