@@ -19,45 +19,7 @@ from gym_cooking_amd.engine import CpuStepper
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-
-class Dev:
-    """oc_belief_update on guard-filled device buffers, numpy in and out (as belief_ref.host_call)."""
-
-    def __init__(self, level, A, B):
-        from gym_cooking_amd.engine import OvercookedBatch
-        self.eb = OvercookedBatch(level, A, B, max_T=100, device="cuda:0")
-
-    def launcher(self, prev, taken, events, rows, agents, flags, bel, bs, want_map=True, want_info=True):
-        M, P = len(agents), self.eb.pitch
-        up = lambda a: None if a is None else torch.from_numpy(a).cuda()  # noqa: E731
-        dbel, dbs = up(bel), up(bs)
-        amap = torch.full((M, P), br.GUARD_MAP, dtype=torch.uint8, device="cuda:0") if want_map else None
-        info = torch.full((M, P), br.GUARD_INFO, dtype=torch.uint8, device="cuda:0") if want_info else None
-        launch = self.eb.belief_update_launcher(up(prev), up(taken), rows, agents, dbel, dbs, up(events), 1.3, 0.5, flags,
-                                                amap, info)
-        return launch, (dbel, dbs, amap, info)
-
-    def call(self, *args, **kw):
-        launch, out = self.launcher(*args, **kw)
-        launch()
-        torch.cuda.synchronize()
-        return tuple(None if t is None else t.cpu().numpy() for t in out)
-
-
-def assert_same(dev, host, S, B, where=""):
-    """bstate, info and the guard columns byte for byte, beliefs to 1e-12 (exp and fused
-    multiply-adds differ in their last bits), map against the device's own beliefs."""
-    dbel, dbs, dmap, dinfo = dev
-    hbel, hbs, _, hinfo = host
-    assert np.array_equal(dbs, hbs), (where, np.argwhere(dbs != hbs)[:5])
-    if dinfo is not None:
-        assert np.array_equal(dinfo, hinfo), (where, np.argwhere(dinfo != hinfo)[:5])
-    err = np.abs(dbel[:, :, :B] - hbel[:, :, :B])
-    assert (err <= br.RTOL * np.abs(hbel[:, :, :B])).all(), (where, err.max())
-    assert np.array_equal(dbel[:, :, B:].view(np.uint64), hbel[:, :, B:].view(np.uint64)), where
-    if dmap is not None:
-        br.check_map(dbel, dbs, dmap, S, B, where)
-        assert (dmap[:, B:] == br.GUARD_MAP).all(), where
+from oc_devlib import BeliefDev as Dev, belief_assert_same as assert_same  # noqa: E402
 
 
 @functools.lru_cache(maxsize=None)

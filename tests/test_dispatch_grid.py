@@ -15,6 +15,7 @@ B = 7: one full word of four envs and one ragged word.  The narrow kitchen is of
 SWAR step and its K = 8 / 16 cells MODE 1; its 12-item level repeats the foods (counts encoding).
 tests/test_dispatch_grid_gpu.py runs the same cells through the kernels."""
 import functools
+import os
 import types
 
 import numpy as np
@@ -49,6 +50,23 @@ def grid_level(K: int, shape: str) -> levels.Level:
     lv = levels.parse_level_text("\n".join(rows) + "\n\nSalad\n\n" + spawns, "grid-%s-%d" % (shape, K))
     assert len(lv.items) == len(items) and capi.item_slots(lv) == K
     assert capi.is_wide(lv) == (shape == "wide") and not lv.edge
+    return lv
+
+
+@functools.lru_cache(maxsize=None)
+def dense_level(K: int) -> levels.Level:
+    """tests/golden/levels/dense-15x17_salad.txt (255 cells, byte cell ids; its lattice of
+    free-standing interior counters makes a 417-node reachability graph) with ITEMS[K] in place of
+    its own items, on the bottom counter row from x = 1 (Floor above each).  The planner kernels
+    of tests/test_plan_grid.py read such a level's distance table from device memory."""
+    with open(os.path.join(tl.GOLDEN, "levels", "dense-15x17_salad.txt")) as f:
+        grid, rest = f.read().split("\n\n", 1)
+    rows = [r.translate(str.maketrans("tlop", "----")) for r in grid.split("\n")]
+    items = ITEMS[K]
+    rows[-1] = rows[-1][0] + items + rows[-1][1 + len(items):]
+    lv = levels.parse_level_text("\n".join(rows) + "\n\n" + rest, "grid-dense-%d" % K)
+    assert len(lv.items) == len(items) and capi.item_slots(lv) == K
+    assert (lv.width, lv.height) == (15, 17) and not capi.is_wide(lv) and not lv.edge
     return lv
 
 

@@ -71,19 +71,13 @@ def check_untouched(act, probs, flags, ref, A, P, B):
     assert (act[:, :B][touched] <= 4).all()
 
 
-@pytest.mark.parametrize("count_state", [False, True])
-@pytest.mark.parametrize("i", range(len(CASES)))
-def test_random_cases_match_oracle_restatement(i, count_state):
-    ob, s, subs, alloc, nc = case(i)
-    ref = reference(i, count_state)
+def assert_matches_restatement(ob, s, subs, alloc, nc, ref, count_state):
+    """oc_cpu_nav_policy on a case against `ref` (policy_ref.distribution of it in that count
+    mode): flags, support, probabilities, the bytes nobody may touch, the GREEDY actions, and the
+    SAMPLE draw replayed from the returned probabilities.  Returns the replayed picks (-1 where the
+    row is not POL_OK)."""
     A, B, P = ob.A, ob.B, ob.pitch
     ok = ref["flags"] == capi.POL_OK
-    _, _, _, _, _, min_ok, min_joint, min_goal = CASES[i]
-    # the conditions of the issue, counted with the oracle alone
-    assert ok.sum() >= min_ok and (ok & ref["joint"]).sum() >= min_joint
-    assert ((ref["probs"] > 0).sum(0)[ok] >= 2).all()
-    if not count_state:
-        assert ref["goal_reach"].sum() >= min_goal
     cmode = STATE if count_state else TABLE
     act_g, probs, flags = host_policy(ob.level, A, B, s, subs, alloc, GREEDY | cmode, nc)
     assert np.array_equal(flags[:B], ref["flags"]), np.argwhere(flags[:B] != ref["flags"])[:5]
@@ -102,6 +96,22 @@ def test_random_cases_match_oracle_restatement(i, count_state):
         u = policy_ref.draw_u(1234, 5 + int(e), 7, int(ref["agent0"][e]))
         pick[e] = policy_ref.replay_draw(probs_s[:, e], int(ref["ncand"][e]), u)
     assert np.array_equal(act_s, policy_ref.expected_actions(ref, pick, before, A, P, B))
+    return pick
+
+
+@pytest.mark.parametrize("count_state", [False, True])
+@pytest.mark.parametrize("i", range(len(CASES)))
+def test_random_cases_match_oracle_restatement(i, count_state):
+    ob, s, subs, alloc, nc = case(i)
+    ref = reference(i, count_state)
+    ok = ref["flags"] == capi.POL_OK
+    _, _, _, _, _, min_ok, min_joint, min_goal = CASES[i]
+    # the conditions of the issue, counted with the oracle alone
+    assert ok.sum() >= min_ok and (ok & ref["joint"]).sum() >= min_joint
+    assert ((ref["probs"] > 0).sum(0)[ok] >= 2).all()
+    if not count_state:
+        assert ref["goal_reach"].sum() >= min_goal
+    pick = assert_matches_restatement(ob, s, subs, alloc, nc, ref, count_state)
     assert len(np.unique(pick[ok])) >= 4  # the draw spreads over the candidates
 
 

@@ -62,10 +62,11 @@ def test_host_rollout_matches_reference_rows(name, level, cfg):
     assert not errs, "\n".join(errs[:20])
 
 
-def random_rollout_case(level_name, A, B, seed, steps=40, planner_levels=(0,)):
-    """Random mid-episode states (oracle goal-free random streams) x random subtask tables."""
+def random_rollout_case(level, A, B, seed, steps=40, planner_levels=(0,)):
+    """Random mid-episode states (oracle goal-free random streams) x random subtask tables, on a
+    level given by name or as a levels.Level."""
     rng = np.random.default_rng(seed)
-    lv = levels.load_level(level_name)
+    lv = levels.load_level(level) if isinstance(level, str) else level
     ob = oracle.OracleBatch(lv, A, 1000, B)
     s, s2 = ob.new_state(), ob.new_state()
     ob.reset(s)

@@ -17,35 +17,9 @@ from gym_cooking_amd.engine import CpuStepper
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+from oc_devlib import TaskDev as Dev, task_assert_same as assert_same  # noqa: E402
+
 CD = tr.COMMIT | tr.DISTINCT
-
-
-class Dev:
-    """oc_task_select on guard-filled device buffers, numpy in and out (as taskselect_ref.host_call)."""
-
-    def __init__(self, level, A, B):
-        from gym_cooking_amd.engine import OvercookedBatch
-        self.eb = OvercookedBatch(level, A, B, max_T=100, device="cuda:0")
-
-    def call(self, s, prev, rows, agents, flags, ts, want_bound=True, want_info=True):
-        M, P = len(agents), self.eb.pitch
-        dts = torch.from_numpy(ts).cuda()
-        bound = torch.full((M, P), float("nan"), dtype=torch.float32, device="cuda:0") if want_bound else None
-        info = torch.full((M, P), tr.GUARD_INFO, dtype=torch.uint8, device="cuda:0") if want_info else None
-        launch = self.eb.task_select_launcher(torch.from_numpy(s).cuda(), rows, agents, dts,
-                                              None if prev is None else torch.from_numpy(prev).cuda(), flags, bound, info)
-        launch()
-        torch.cuda.synchronize()
-        return (dts.cpu().numpy(), None if bound is None else bound.cpu().numpy(),
-                None if info is None else info.cpu().numpy())
-
-
-def assert_same(dev, host):
-    """Byte-equal, the guard columns (0xC3 task state, NaN bound, 0xA5 info) included."""
-    for d, h in zip(dev, host):
-        assert (d is None) == (h is None)
-        if d is not None:
-            assert np.array_equal(d.view(np.uint8), h.view(np.uint8)), np.argwhere(d.view(np.uint8) != h.view(np.uint8))[:5]
 
 
 @functools.lru_cache(maxsize=None)
