@@ -1419,6 +1419,38 @@ __global__ __launch_bounds__(kBlock) void oc_task_kernel(RollArgs R, TaskArgs Q,
     }
 }
 
+// Joint and split subtask choice of one pair of scripted agents (oc_team_select), a sibling of
+// oc_task_kernel: one env per lane, the tables and the 3 x S configurations (a0's one-agent rows,
+// a1's, the two-agent rows) staged as there, hold_cells and bound_row once per env, the subtasks
+// walked with a wave-uniform index (ocro::RowOps::team_env: a subtask no lane of the wave has open
+// costs none of its three bounds).  The rule's state across the walk is scalars, so nothing is
+// indexed by the subtask and nothing goes to scratch for it.  Every plane access of a wave covers
+// 64 consecutive envs of one plane.  The two-agent bound reads the agent-pair table where the
+// level has one, as oc_bounds_kernel does (the same bytes either way).
+struct TeamArgs {
+    int32_t S, flags;
+};
+template <int A, int K, bool W, bool GD>
+__global__ __launch_bounds__(kBlock) void oc_team_kernel(RollArgs R, TeamArgs Q, const uint8_t* __restrict__ sin,
+                                                         const uint8_t* __restrict__ sprev,
+                                                         const uint8_t* __restrict__ blob_g, uint8_t* __restrict__ ts,
+                                                         float* __restrict__ bound, uint8_t* __restrict__ info) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t blob_w[];
+    __shared__ ocro::Sub subs[OC_MAX_SUBTASKS];
+    stage_roll_tables(R, blob_g, blob_w, subs);
+    const uint8_t* blob = (const uint8_t*)blob_w;
+    const int64_t P = R.pitch;
+    using PL = Planes<A, K, W>;
+    for (int64_t e = blockIdx.x * (int64_t)kBlock + threadIdx.x; e < R.B; e += (int64_t)gridDim.x * kBlock) {
+        const ocro::RowT<K, W> r = load_row<A, K, W>(sin, P, e);
+        const bool init = (Q.flags & OC_TEAM_INIT) != 0 || (sprev != nullptr && (sprev[PL::F * P + e] & OC_FLAG_DONE) != 0);
+        ocro::RowOps<A, K, W, false, GD> ops(R.L, blob, GD ? blob_g + R.L.dist_off : blob + R.L.dist_off);  // distances: LDS (narrow), device memory (wide)
+        ops.PT = R.L.pair_off != 0 ? (const uint32_t*)(blob_g + R.L.pair_off) : nullptr;  // the agent-pair table (device memory)
+        ops.team_env(r, subs, Q.S, Q.flags, init, ts + e, bound != nullptr ? bound + e : nullptr,
+                     info != nullptr ? info + e : nullptr, P);
+    }
+}
+
 // The posterior over a watched agent's subtask (oc_belief_update), a sibling of oc_policy_kernel:
 // a group of 8 lanes per (env, watched agent), the watched agent m = blockIdx.y (the watched agents
 // of an env do not depend on each other).  What the S one-agent hypotheses about one agent share
@@ -3337,6 +3369,104 @@ int oc_cpu_task_select(const oc_handle* h, const void* state, const void* state_
                              bound != nullptr ? bound + e : nullptr, info != nullptr ? info + e : nullptr, P);
             }
             return OC_OK;
+        });
+    });
+}
+
+// oc_team_select / oc_cpu_team_select: the arguments both check, and the call's RollArgs (a0's S
+// one-agent Level-0 configurations at rows 0 .., a1's at S .., the two-agent ones at 2S ..) and
+// TeamArgs
+static int team_args(const oc_handle* h, const void* state, const oc_subtask* subtasks, int32_t num_subtasks,
+                     const uint8_t* agents, int32_t flags, const uint8_t* tstate, const float* bound, int64_t B,
+                     bool host, RollArgs& R, TeamArgs& Q) {
+    if (state == nullptr || subtasks == nullptr || agents == nullptr || tstate == nullptr)
+        return fail(OC_EINVAL, "team_select: state, subtasks, agents and tstate are required");
+    if (B < 0) return fail(OC_EINVAL, "team_select: B %lld", (long long)B);
+    const int32_t S = num_subtasks;
+    if (h->A < 2) return fail(OC_EINVAL, "team_select: a team needs 2 agents, the handle has %d", h->A);
+    if (S < 1 || S > OC_TEAM_MAX_SUBTASKS)
+        return fail(OC_EINVAL, "team_select: num_subtasks %d (1..%d)", S, OC_TEAM_MAX_SUBTASKS);
+    if (flags < 0 || flags > (OC_TEAM_INIT | OC_TEAM_COMMIT | OC_TEAM_SPLIT_FIRST))
+        return fail(OC_EINVAL, "team_select: flags %d", flags);
+    if (agents[0] >= h->A || agents[1] >= h->A)
+        return fail(OC_EINVAL, "team_select: agent %d", agents[0] >= h->A ? agents[0] : agents[1]);
+    if (agents[0] >= agents[1]) return fail(OC_EINVAL, "team_select: agents %d, %d not ascending", agents[0], agents[1]);
+    if (((uintptr_t)bound & 3u) || ((uintptr_t)state & 1u)) return fail(OC_EINVAL, "team_select: misaligned buffer");
+    static_assert(3 * OC_TEAM_MAX_SUBTASKS <= OC_MAX_SUBTASKS, "the three configurations per subtask share the staging");
+    oc_subtask rows[OC_MAX_SUBTASKS];
+    for (int c = 0; c < 3; ++c)
+        for (int i = 0; i < S; ++i) {
+            oc_subtask& d = rows[c * S + i];
+            d = oc_subtask{};
+            d.kind = subtasks[i].kind;
+            d.num_agents = c == 2 && d.kind != OC_SUB_NONE ? 2 : 1;  // a None row is a one-agent row and never a candidate
+            d.agent[0] = agents[c == 1 ? 1 : 0];
+            if (d.num_agents == 2) d.agent[1] = agents[1];
+            d.start_mask[0] = subtasks[i].start_mask[0];
+            d.start_mask[1] = subtasks[i].start_mask[1];
+            d.goal_mask = subtasks[i].goal_mask;
+            d.level = OC_LEVEL0;
+        }
+    if (const int rc = roll_args(h, rows, 3 * S, B, R, false, host)) return rc;
+    Q.S = S;
+    Q.flags = flags;
+    return OC_OK;
+}
+
+int oc_team_select(const oc_handle* h, const void* state, const void* state_prev, const oc_subtask* subtasks,
+                   int32_t num_subtasks, const uint8_t* agents, int32_t flags, uint8_t* tstate, float* bound,
+                   uint8_t* info, int64_t B, void* stream) {
+    if (h == nullptr) return fail(OC_EINVAL, "bad argument");
+    ErrScope es_(h);
+    OC_NEED_DEVICE(h);
+    RollArgs R;
+    TeamArgs Q;
+    if (const int rc = team_args(h, state, subtasks, num_subtasks, agents, flags, tstate, bound, B, false, R, Q)) return rc;
+    if (B == 0) return OC_OK;
+    const int64_t need = (B + kBlock - 1) / kBlock, cap = (int64_t)h->cus * 8;
+    const dim3 grid((unsigned)(need < cap ? need : cap));
+    hipStream_t st = (hipStream_t)stream;
+    return dispatch_plan(h, [&](auto a, auto k, auto w, auto gd) {
+        if constexpr (decltype(a)::value < 2) {
+            return fail(OC_EINVAL, "team_select: a team needs 2 agents");
+        } else {
+            const auto kernel = oc_team_kernel<a(), k(), w(), gd()>;
+            if (const int rc = allow_dyn_lds((const void*)kernel, R.blob_words * 4)) return rc;
+            hipLaunchKernelGGL(kernel, grid, dim3(kBlock), R.blob_words * 4, st, R, Q, (const uint8_t*)state,
+                               (const uint8_t*)state_prev, h->roll_blob, tstate, bound, info);
+            return hip_check("oc_team_select launch");
+        }
+    });
+}
+
+int oc_cpu_team_select(const oc_handle* h, const void* state, const void* state_prev, const oc_subtask* subtasks,
+                       int32_t num_subtasks, const uint8_t* agents, int32_t flags, uint8_t* tstate, float* bound,
+                       uint8_t* info, int64_t B, int32_t nthreads) {
+    if (h == nullptr || nthreads < 0) return fail(OC_EINVAL, "bad argument");
+    ErrScope es_(h);
+    RollArgs R;
+    TeamArgs Q;
+    if (const int rc = team_args(h, state, subtasks, num_subtasks, agents, flags, tstate, bound, B, true, R, Q)) return rc;
+    if (B == 0) return OC_OK;
+    const int64_t nt = host_threads(nthreads, B, 1024);  // >= 1,024 rows (up to 3 x S bound walks each) per thread
+    const uint8_t* blob = h->roll_blob_host.data();
+    const uint8_t *sin = (const uint8_t*)state, *sprev = (const uint8_t*)state_prev;
+    return run_ranges(nt, [&](int64_t i) {
+        const int64_t e0 = B * i / nt, e1 = B * (i + 1) / nt;
+        return dispatch_w(h, [&](auto a, auto k, auto w) {
+            if constexpr (decltype(a)::value < 2) {
+                return fail(OC_EINVAL, "team_select: a team needs 2 agents");
+            } else {
+                using PL = Planes<a(), k(), w()>;
+                const int64_t P = R.pitch;
+                for (int64_t e = e0; e < e1; ++e) {
+                    const bool init = (Q.flags & OC_TEAM_INIT) != 0 || (sprev != nullptr && (sprev[PL::F * P + e] & OC_FLAG_DONE) != 0);
+                    ocro::RowOps<a(), k(), w(), false, true> ops(R.L, blob);
+                    ops.team_env(load_row<a(), k(), w()>(sin, P, e), R.subs, Q.S, Q.flags, init, tstate + e,
+                                 bound != nullptr ? bound + e : nullptr, info != nullptr ? info + e : nullptr, P);
+                }
+                return OC_OK;
+            }
         });
     });
 }

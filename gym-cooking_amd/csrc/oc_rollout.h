@@ -1424,6 +1424,167 @@ struct RowOps {
         }
     }
 
+    // ---- oc_team_select: joint and split subtask choice of one pair of scripted agents --------
+    // One env of oc_team_select (include/oc_engine.h, "The rule"): the pair a0 < a1, a0's one-agent
+    // configurations in subs[0 .. S), a1's in subs[S .. 2S), the two-agent ones in subs[2S .. 3S).
+    // ts / bound / info point at column e of the call's buffers (planes P apart); the env's bytes
+    // are read before they are written.  refresh_subtasks (utils/agent.py:151-171), then the
+    // heaviest allocation of add_subtasks' space (bayesian_delegator.py:697-886) under
+    // get_spatial_priors' weight (:296-369) over the doable rows (prune_subtask_allocs :200-256).
+    // What the walk carries is scalars only (two (w, index, lb) pairs per member, the joint best,
+    // the three "current member is a candidate" bits): nothing is indexed by the subtask.  A subtask
+    // no lane of the wave has open costs none of its three bound walks (wave_any; every lane of the
+    // host build is its own wave).
+    OC_RH void team_env(Row r, const Sub* subs, int S, int flags, bool init, uint8_t* ts, float* bound, uint8_t* info,
+                        int64_t P) {
+        const int EP = (S + 7) >> 3, kOut = 0xFF;
+        hold_cells(r);
+        const BoundRow br = bound_row<true>(r);
+        const uint32_t all = (1u << S) - 1u;
+        uint32_t inc = 0u;
+        for (int c = 0; c < EP; ++c) inc |= (uint32_t)ts[c * P] << (8 * c);
+        inc &= all;
+        int cur0 = ts[EP * P], cur1 = ts[(EP + 1) * P], curJ = ts[(EP + 2) * P];
+        int cnt0 = ts[(EP + 3) * P], cnt1 = ts[(EP + 4) * P], fl = 0;
+        if (init) {
+            inc = all;
+            cur0 = cur1 = S;
+            curJ = kOut;
+            cnt0 = cnt1 = 0;
+            fl = 8;  // OC_TEAMF_REINIT
+        }
+        const int e0 = cur0, e1 = cur1, eJ = curJ;
+        // refresh: the counts of the current members (evaluated on every lane, used where a member is
+        // a subtask); the count of row i does not depend on the agents of the row
+        {
+            int n0 = 0, n1 = 0, nJ = 0;
+            // kept rolled (q is wave-uniform): one copy of the count and, below, of the bound walk per
+            // kernel build, not three
+#pragma unroll 1
+            for (int q = 0; q < 3; ++q) {
+                const int c = q == 0 ? cur0 : q == 1 ? cur1 : curJ;
+                const int n = goal_objects(r, subs[c < S ? c : 0]);
+                if (q == 0) n0 = n;
+                else if (q == 1) n1 = n;
+                else nJ = n;
+            }
+            if (curJ < S) {
+                if (nJ > cnt0) {
+                    inc &= ~(1u << curJ);
+                    fl |= 3;  // OC_TEAMF_COMPLETED0 | OC_TEAMF_COMPLETED1
+                }
+            } else {
+                if (cur0 < S && n0 > cnt0) {
+                    inc &= ~(1u << cur0);
+                    fl |= 1;  // OC_TEAMF_COMPLETED0
+                }
+                if (cur1 < S && n1 > cnt1) {
+                    inc &= ~(1u << cur1);
+                    fl |= 2;  // OC_TEAMF_COMPLETED1
+                }
+            }
+        }
+        const bool dropped = (fl & 3) != 0;
+        if (dropped) {
+            cur0 = cur1 = S;
+            curJ = kOut;
+        }
+        // candidates: the two heaviest of each member, the heaviest joint one, and whether the
+        // current members are candidates (> keeps the lowest index among equal weights)
+        int f0 = S, s0 = S, f1 = S, s1 = S, iJ = S;
+        double wf0 = 0.0, ws0 = 0.0, wf1 = 0.0, ws1 = 0.0, wJ = 0.0;
+        float lf0 = 0.0f, ls0 = 0.0f, lf1 = 0.0f, ls1 = 0.0f, lJ = 0.0f, k0lb = 0.0f, k1lb = 0.0f, kJlb = 0.0f;
+        bool k0 = false, k1 = false, kJ = false;
+#pragma unroll 1
+        for (int i = 0; i < S; ++i) {
+            const bool want = ((inc >> i) & 1u) != 0u && subs[i].kind != 0;
+            if (!wave_any(want)) continue;  // wave-uniform
+#pragma unroll 1
+            for (int q = 0; q < 3; ++q) {  // a0's row, a1's row, the two-agent row: q is wave-uniform
+                float lb;
+                if (!(full_bound(br, r, subs[q * S + i], lb) && want)) continue;
+                const double w = 1.0 / (double)lb;
+                if (q == 0) {
+                    if (f0 == S || w > wf0) {
+                        s0 = f0, ws0 = wf0, ls0 = lf0;
+                        f0 = i, wf0 = w, lf0 = lb;
+                    } else if (s0 == S || w > ws0) {
+                        s0 = i, ws0 = w, ls0 = lb;
+                    }
+                    if (i == cur0) k0 = true, k0lb = lb;
+                } else if (q == 1) {
+                    if (f1 == S || w > wf1) {
+                        s1 = f1, ws1 = wf1, ls1 = lf1;
+                        f1 = i, wf1 = w, lf1 = lb;
+                    } else if (s1 == S || w > ws1) {
+                        s1 = i, ws1 = w, ls1 = lb;
+                    }
+                    if (i == cur1) k1 = true, k1lb = lb;
+                } else {
+                    if (iJ == S || w > wJ) iJ = i, wJ = w, lJ = lb;
+                    if (i == curJ) kJ = true, kJlb = lb;
+                }
+            }
+        }
+        float b0 = 0.0f, b1 = 0.0f;
+        const bool keep = (flags & 2) && !dropped && (curJ < S ? kJ : cur0 < S && cur1 < S && k0 && k1);  // OC_TEAM_COMMIT
+        if (keep) {
+            b0 = curJ < S ? kJlb : k0lb;
+            b1 = curJ < S ? kJlb : k1lb;
+        } else {
+            // the split pick: the argmax of w0_i + w1_j over i != j, None (S, +0.0) allowed for one member
+            int p0 = f0, p1 = f1;
+            double wS = wf0 + wf1;  // a member without candidates weighs +0.0
+            float q0 = lf0, q1 = lf1;
+            const bool have = f0 < S || f1 < S;
+            if (have && f0 == f1) {
+                const double x = wf0 + ws1, y = ws0 + wf1;
+                if (x >= y) p1 = s1, q1 = ls1, wS = x;
+                else p0 = s0, q0 = ls0, wS = y;
+            }
+            const bool full = p0 < S && p1 < S;
+            if ((flags & 4) && have && full) {  // OC_TEAM_SPLIT_FIRST
+                cur0 = p0, cur1 = p1, curJ = kOut;
+                b0 = q0, b1 = q1;
+            } else if (iJ < S && (!have || wJ >= wS)) {
+                cur0 = cur1 = kOut, curJ = iJ;
+                b0 = b1 = lJ;
+            } else if (have) {
+                cur0 = p0, cur1 = p1, curJ = kOut;
+                b0 = q0, b1 = q1;
+            } else {
+                cur0 = cur1 = S, curJ = kOut;
+                fl |= 0x20;  // OC_TEAMF_IDLE
+            }
+        }
+        if (cur0 != e0 || cur1 != e1 || curJ != eJ) {
+            fl |= 4;  // OC_TEAMF_SWITCHED
+            const int m0 = curJ < S ? curJ : cur0;  // a0's member
+            int n0 = 0, n1 = 0;
+#pragma unroll 1
+            for (int q = 0; q < 2; ++q) {
+                const int c = q == 0 ? m0 : cur1;
+                const int n = goal_objects(r, subs[c < S ? c : 0]);
+                if (q == 0) n0 = n;
+                else n1 = n;
+            }
+            cnt0 = curJ < S || cur0 < S ? n0 : 0;
+            cnt1 = curJ >= S && cur1 < S ? n1 : 0;
+        }
+        if (curJ < S) fl |= 0x10;  // OC_TEAMF_JOINT
+        for (int c = 0; c < EP; ++c) ts[c * P] = (uint8_t)(inc >> (8 * c));
+        ts[EP * P] = (uint8_t)cur0;
+        ts[(EP + 1) * P] = (uint8_t)cur1;
+        ts[(EP + 2) * P] = (uint8_t)curJ;
+        ts[(EP + 3) * P] = (uint8_t)cnt0;
+        ts[(EP + 4) * P] = (uint8_t)cnt1;
+        if (bound != nullptr) {
+            bound[0] = b0;
+            bound[P] = b1;
+        }
+        if (info != nullptr) info[0] = (uint8_t)fl;
+    }
+
     // ---- oc_belief_update: the posterior over a watched agent's subtask ----------------------
     // One (env, watched agent a) of oc_belief_update (include/oc_engine.h, "The rule"), the whole
     // row on one lane: the host call's row (the kernel spreads the same steps over a lane group).

@@ -40,7 +40,7 @@ EXPORTED_SYMBOLS = (
     "oc_set_likelihood_form", "oc_observe", "oc_cpu_observe", "oc_progress", "oc_cpu_progress",
     "oc_set_start_cells", "oc_get_start_cells", "oc_reset_random", "oc_cpu_reset_random",
     "oc_nav_policy", "oc_cpu_nav_policy", "oc_task_select", "oc_cpu_task_select",
-    "oc_belief_update", "oc_cpu_belief_update",
+    "oc_belief_update", "oc_cpu_belief_update", "oc_team_select", "oc_cpu_team_select",
 )
 
 # oc_belief_update: the call flag, and the per-(env, watched agent) info bits
@@ -50,6 +50,12 @@ BELF_UPDATED, BELF_PRUNED, BELF_REINIT, BELF_RESET, BELF_RAISED = 0x01, 0x02, 0x
 # oc_task_select: call flags, and the per-agent info bits
 OC_TASK_INIT, OC_TASK_COMMIT, OC_TASK_DISTINCT = 1, 2, 4
 TASKF_COMPLETED, TASKF_SWITCHED, TASKF_REINIT = 0x01, 0x02, 0x04
+
+# oc_team_select: call flags, the per-env info bits, and the cur byte of an env outside a plane's launch
+OC_TEAM_INIT, OC_TEAM_COMMIT, OC_TEAM_SPLIT_FIRST = 1, 2, 4
+TEAMF_COMPLETED0, TEAMF_COMPLETED1, TEAMF_SWITCHED, TEAMF_REINIT, TEAMF_JOINT, TEAMF_IDLE = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20
+OC_TEAM_OUT = 0xFF
+OC_TEAM_MAX_SUBTASKS = 21
 
 # oc_nav_policy: row flags, and the mode bits (bit 0 the choice, bit 1 the goal count)
 POL_OK, POL_RAISES, POL_BADALLOC = 0x01, 0x04, 0x80
@@ -80,6 +86,12 @@ def task_planes(S: int) -> int:
     """Byte planes of one scripted agent's oc_task_select state for S subtasks (OC_TASK_PLANES):
     the incomplete set (event_planes(S) planes), then cur, then cnt."""
     return event_planes(S) + 2
+
+
+def team_planes(S: int) -> int:
+    """Byte planes of a pair's oc_team_select state for S subtasks (OC_TEAM_PLANES): the incomplete
+    set (event_planes(S) planes), then cur0, cur1, curJ (the three `alloc` planes), then cnt0, cnt1."""
+    return event_planes(S) + 5
 
 
 def belief_planes(S: int) -> int:
@@ -317,6 +329,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.oc_task_select.argtypes = [vp, vp, vp, ctypes.POINTER(OcSubtask), i32, vp, i32, i32, vp, vp, vp, i64, vp]
     lib.oc_cpu_task_select.restype = ctypes.c_int
     lib.oc_cpu_task_select.argtypes = [vp, vp, vp, ctypes.POINTER(OcSubtask), i32, vp, i32, i32, vp, vp, vp, i64, i32]
+    lib.oc_team_select.restype = ctypes.c_int
+    lib.oc_team_select.argtypes = [vp, vp, vp, ctypes.POINTER(OcSubtask), i32, vp, i32, vp, vp, vp, i64, vp]
+    lib.oc_cpu_team_select.restype = ctypes.c_int
+    lib.oc_cpu_team_select.argtypes = [vp, vp, vp, ctypes.POINTER(OcSubtask), i32, vp, i32, vp, vp, vp, i64, i32]
     lib.oc_belief_update.restype = ctypes.c_int
     lib.oc_belief_update.argtypes = [vp, vp, vp, vp, ctypes.POINTER(OcSubtask), i32, vp, i32, ctypes.c_double,
                                      ctypes.c_double, i32, vp, vp, vp, vp, i64, vp]

@@ -367,6 +367,48 @@ class OvercookedBatch(_StartCells):
                 _ptr(bound), _ptr(info), self.B, self._stream())
         return _bound(self.lib.oc_task_select, args)
 
+    def new_team_state(self, S: int) -> torch.Tensor:
+        """u8 [capi.team_planes(S), pitch] team state of one pair of scripted agents over S subtasks
+        (oc_team_select), zeroed; the first call on it passes capi.OC_TEAM_INIT."""
+        return torch.zeros((capi.team_planes(S), self.pitch), dtype=torch.uint8, device=self.device)
+
+    def team_select(self, state: torch.Tensor, subtasks, pair, tstate: torch.Tensor,
+                    prev: Optional[torch.Tensor] = None, flags: int = capi.OC_TEAM_COMMIT,
+                    bound: Optional[torch.Tensor] = None, info: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Per-env joint or split subtask choice of the scripted pair `pair` = (a0, a1), a0 < a1
+        (oc_team_select): the reference agent's refresh_subtasks over `tstate` (new_team_state;
+        updated in place), then the heaviest allocation under the spatial prior, the sum of
+        1 / lower bound over its members: both agents on one subtask, or each on its own.  With EP =
+        capi.event_planes(S) the planes tstate[EP], tstate[EP + 1] and tstate[EP + 2] are
+        nav_policy's `alloc` for a0's one-agent table (subtasks + [None]), a1's, and the two-agent
+        table; an env outside a table holds capi.OC_TEAM_OUT there and that launch skips it
+        (capi.POL_BADALLOC).  `prev`, capi.OC_TEAM_INIT and `bound` (f32 [2, pitch]) as task_select.
+        Returns info u8 [pitch] (capi.TEAMF_*)."""
+        if info is None:
+            info = torch.empty(self.pitch, dtype=torch.uint8, device=self.device)
+        self.team_select_launcher(state, subtasks, pair, tstate, prev, flags, bound, info)()
+        return info
+
+    def team_select_launcher(self, state: torch.Tensor, subtasks, pair, tstate: torch.Tensor,
+                             prev: Optional[torch.Tensor], flags: int, bound: Optional[torch.Tensor],
+                             info: Optional[torch.Tensor]):
+        """An oc_team_select call bound once (see rollout_launcher)."""
+        S = len(subtasks)
+        if len(pair) != 2:
+            raise ValueError("team_select: a pair of agents, got %r" % (tuple(pair),))
+        self._check(state, self.layout.state_bytes)
+        if prev is not None:
+            self._check(prev, self.layout.state_bytes)
+        self._check(tstate, capi.team_planes(S) * self.pitch)
+        if bound is not None:
+            self._check(bound, 4 * 2 * self.pitch, (torch.float32,))
+        if info is not None:
+            self._check(info, self.pitch)
+        ags = (ctypes.c_uint8 * 2)(*[int(a) for a in pair])
+        args = (self._h, _ptr(state), _ptr(prev), capi.subtask_array(subtasks), S, ags, int(flags), _ptr(tstate),
+                _ptr(bound), _ptr(info), self.B, self._stream())
+        return _bound(self.lib.oc_team_select, args)
+
     def new_belief_state(self, S: int, M: int):
         """Buffers of oc_belief_update for M watched agents over S subtasks, zeroed: (belief f64
         [M, S + 1, pitch], bstate u8 [M, 2 * capi.belief_planes(S), pitch], map u8 [M, pitch], info
@@ -687,6 +729,28 @@ class CpuStepper(_StartCells):
         p = lambda a: None if a is None else a.ctypes.data  # noqa: E731
         ags = (ctypes.c_uint8 * M)(*[int(a) for a in agents])
         capi.check(self.lib.oc_cpu_task_select(self._h, p(state), p(prev), capi.subtask_array(subtasks), S, ags, M,
+                                               int(flags), p(tstate), p(bound), p(info), B, self.nthreads))
+        return info
+
+    def team_select(self, state: np.ndarray, subtasks, pair, tstate: np.ndarray, prev: Optional[np.ndarray] = None,
+                    flags: int = capi.OC_TEAM_COMMIT, bound: Optional[np.ndarray] = None,
+                    info: Optional[np.ndarray] = None) -> np.ndarray:
+        """oc_cpu_team_select: the scripted pair's joint or split subtask choice in the host buffers;
+        mirrors OvercookedBatch.team_select.  `tstate` u8 [capi.team_planes(S), pitch] is updated in
+        place, `bound` f32 [2, pitch] when given; only columns below B are written (buffers may end
+        at column B of their last plane).  Returns info u8 [pitch]."""
+        S, B, P = len(subtasks), self.B, self.pitch
+        if len(pair) != 2:
+            raise ValueError("team_select: a pair of agents, got %r" % (tuple(pair),))
+        info = np.zeros(P, np.uint8) if info is None else info
+        for a, n, dt in ((state, self.layout.state_bytes, np.uint8), (prev, self.layout.state_bytes, np.uint8),
+                         (tstate, (capi.team_planes(S) - 1) * P + B, np.uint8), (info, B, np.uint8),
+                         (bound, 4 * (P + B), np.float32)):
+            if a is not None and (a.dtype != dt or not a.flags.c_contiguous or a.nbytes < n):
+                raise ValueError("host buffers: contiguous %s of at least %d bytes" % (np.dtype(dt), n))
+        p = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        ags = (ctypes.c_uint8 * 2)(*[int(a) for a in pair])
+        capi.check(self.lib.oc_cpu_team_select(self._h, p(state), p(prev), capi.subtask_array(subtasks), S, ags,
                                                int(flags), p(tstate), p(bound), p(info), B, self.nthreads))
         return info
 

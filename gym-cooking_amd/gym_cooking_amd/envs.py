@@ -845,6 +845,7 @@ class OvercookedVecEnv:
         self._stepped = False
         self._task_round = None  # partner_tasks(): the next call starts every env over
         self._belief_round = None  # partner_beliefs(): likewise
+        self._team_round = None  # team_tasks(): likewise
         return self.state
 
     def step(self, actions: torch.Tensor):
@@ -1019,6 +1020,67 @@ class OvercookedVecEnv:
             view, _ = self.partner_actions(tables[a], self._task[m, EP], beta, mode, out)
             out = self._partner if out is None else out
         return view, info
+
+    def team_tasks(self, pair, commit: bool = True, split_first: bool = False):
+        """The allocation the scripted pair `pair` = (a0, a1), a0 < a1, follows in the current states
+        (oc_team_select over ``subtasks``): per env either both agents on one subtask (joint) or
+        each on its own (split), the heaviest under the sum of 1 / lower bound over the members;
+        `commit` keeps the current allocation while its members stay candidates, `split_first`
+        prefers a split with two subtasks over any joint one.  The team state lives in this env
+        across step() with partner_tasks' life cycle: the first call after reset() (or with another
+        pair) starts every env over, a call after a step starts over the envs that step auto-reset,
+        and a second call on the same states starts none.  Returns (cur0, cur1, curJ u8 [B]: a
+        subtask index, len(subtasks) for None, capi.OC_TEAM_OUT where the env is not that plane's;
+        info u8 [B] of capi.TEAMF_*), views of this env's buffers."""
+        pair = tuple(int(a) for a in pair)
+        S = len(self.subtasks)
+        if S == 0:
+            raise ValueError("the level's recipes have no subtasks")
+        EP, B = capi.event_planes(S), self.num_envs
+        flags = (capi.OC_TEAM_COMMIT if commit else 0) | (capi.OC_TEAM_SPLIT_FIRST if split_first else 0)
+        if getattr(self, "_team_pair", None) != pair:
+            self._team_pair = pair
+            self._team = self.batch.new_team_state(S)
+            self._team_info = torch.empty(self.P, dtype=torch.uint8, device=self.batch.device)
+            self._team_round = None
+        prev = None
+        if self._team_round is None:
+            flags |= capi.OC_TEAM_INIT
+        elif self._team_round != self._round:  # stepped since: the other buffer is the state before
+            prev = self._s[self._i ^ 1]
+        self._team_round = self._round
+        self.batch.team_select(self.state, self._sub_rows, pair, self._team, prev, flags, None, self._team_info)
+        return self._team[EP, :B], self._team[EP + 1, :B], self._team[EP + 2, :B], self._team_info[:B]
+
+    def team_actions(self, pair, beta: float = 1.3,
+                     mode: int = capi.OC_POLICY_SAMPLE | capi.OC_POLICY_COUNT_STATE,
+                     out: Optional[torch.Tensor] = None, commit: bool = True, split_first: bool = False):
+        """Actions of a scripted pair that drives itself: team_tasks(pair) picks each env's
+        allocation, then three oc_nav_policy launches on one stream act on it: a0's one-agent table
+        (the level's subtasks, then None) with plane cur0 as `alloc`, a1's with plane cur1, and the
+        two-agent table with plane curJ.  An env is written by the launches its allocation names and
+        skipped (capi.POL_BADALLOC) by the others; ``team_flags`` u8 [3, pitch] keeps each launch's
+        flags.  Only the pair's bytes of `out` (u8 [A, pitch]; None: this env's buffer) are written.
+        Returns (the [A, B] view of `out`, team info u8 [B])."""
+        pair = tuple(int(a) for a in pair)
+        *_, info = self.team_tasks(pair, commit, split_first)
+        if out is None:
+            if getattr(self, "_partner", None) is None:
+                self._partner = self.batch.new_actions()
+            out = self._partner
+        if getattr(self, "team_flags", None) is None:
+            self.team_flags = torch.zeros((3, self.P), dtype=torch.uint8, device=self.batch.device)
+        tables = self.__dict__.setdefault("_team_tables", {})
+        if pair not in tables:
+            enc = self.batch.level.encoding
+            tables[pair] = (capi.policy_subtasks(list(self.subtasks) + [None], enc, [pair[0]]),
+                            capi.policy_subtasks(list(self.subtasks) + [None], enc, [pair[1]]),
+                            capi.policy_subtasks(list(self.subtasks), enc, pair))
+        EP = capi.event_planes(len(self.subtasks))
+        for q, (table, ncand) in enumerate(zip(tables[pair], (5, 5, 25))):
+            self.batch.nav_policy(self.state, table, out, beta=beta, mode=mode, alloc=self._team[EP + q], step=self._round,
+                                  seed=self.seed, num_cand=ncand, flags=self.team_flags[q])
+        return out.view(self.A, self.P)[:, :self.num_envs], info
 
     def episode_stats(self) -> torch.Tensor:
         """int64 [episodes, successes, steps, collisions, errors] since construction."""

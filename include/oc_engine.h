@@ -786,6 +786,108 @@ int oc_cpu_task_select(const oc_handle* h, const void* state, const void* state_
                        uint8_t* tstate, float* bound, uint8_t* info, int64_t B, int32_t nthreads);
 
 /* ---------------------------------------------------------------------------------------
+ * Joint and split subtask choice for one pair of scripted agents (additive to ABI 12): the three
+ * bytes three oc_nav_policy launches take as `alloc`, made on the device.  oc_task_select reasons
+ * about "agent a alone follows subtask i"; this call also weighs "both agents follow subtask i",
+ * which is what a kitchen needs whose every subtask takes two agents (full-divider_*: an item is
+ * handed over a counter wall).  Per env, the allocation space of two agents and its pruning:
+ *   add_subtasks, get_other_subtask_allocations   delegation_planner/bayesian_delegator.py:697-886
+ *       cooperative (t, (a0, a1)), and divide-and-conquer (t0, (a0,)), (t1, (a1,)) with t0 != t1;
+ *       None is allowed for one member and not for both
+ *   prune_subtask_allocs                          bayesian_delegator.py:200-256
+ *   subtask_alloc_is_doable                       bayesian_delegator.py:98-156
+ *   get_spatial_priors                            bayesian_delegator.py:296-369
+ *       the weight of an allocation is the sum over its non-None members of
+ *       1 / get_lower_bound_for_subtask_alloc
+ *   refresh_subtasks                              gym_cooking/utils/agent.py:151-171
+ * Build-defined, like oc_task_select: the argmax of the spatial prior in place of BRTDP-valued
+ * priors and Bayesian updates over time, one incomplete set shared by the pair, and the tie rules.
+ *
+ * The team is a0 = agents[0] < a1 = agents[1].  With S = num_subtasks and EP =
+ * OC_PROGRESS_EVENT_PLANES(S), the team state of an env is u8 [OC_TEAM_PLANES(S) = EP + 5][pitch]:
+ *   0 .. EP-1 : the incomplete set, bit b of plane c is subtask 8c + b (oc_progress's events
+ *               numbering); bits >= S are zero
+ *   EP        : cur0    EP + 1 : cur1    EP + 2 : curJ    EP + 3 : cnt0    EP + 4 : cnt1
+ * The allocation is joint iff curJ < S; then cur0 = cur1 = OC_TEAM_OUT.  Otherwise it is split:
+ * cur0 and cur1 are in [0, S], S meaning None, and curJ = OC_TEAM_OUT.  Idle is the split (S, S).
+ * The three cur planes are directly the `alloc` planes of three oc_nav_policy launches: plane cur0
+ * for a0's one-agent table (rows 0 .. S-1 these subtasks, row S None), plane cur1 for a1's, plane
+ * curJ for the two-agent table of S rows.  oc_nav_policy flags an alloc >= its table size
+ * OC_POL_BADALLOC and writes nothing for that row: "this env is not this launch's".
+ *
+ * The rule, for env e (count_i is oc_progress's count_i on `state`):
+ *   1. initialise, if the env is selected for it: incomplete = all S bits, cur0 = cur1 = S, curJ =
+ *      OC_TEAM_OUT, cnt0 = cnt1 = 0.  OC_TEAMF_REINIT
+ *   2. refresh.  Joint: if count_curJ > cnt0, clear bit curJ, OC_TEAMF_COMPLETED0 | COMPLETED1.
+ *      Split: for m = 0, 1: if cur_m < S and count_cur_m > cnt_m, clear bit cur_m,
+ *      OC_TEAMF_COMPLETED_m.  If anything completed the allocation is dropped (cur0 = cur1 = S,
+ *      curJ = OC_TEAM_OUT) and step 4 cannot keep it
+ *   3. candidates, over every i < S with bit i set and kind != OC_SUB_NONE:
+ *        C0: the row {kind_i, 1 agent {a0}, masks_i} is doable;  C1: the same for a1;
+ *        CJ: the row {kind_i, 2 agents {a0, a1}, masks_i} is doable
+ *      doable and lb are exactly oc_subtask_bounds' outputs on `state`.  The weights are f64,
+ *      w = 1.0 / (double)lb (lb >= 1, world.py:264); None weighs +0.0
+ *   4. keep, with OC_TEAM_COMMIT when step 2 dropped nothing.  Joint: curJ in CJ.  Split: cur0 < S,
+ *      cur1 < S, cur0 in C0 and cur1 in C1 (an allocation with a None member is never kept).  Then
+ *      the allocation and the counts stay; go to 7
+ *   5. picks.  first_m = the i in C_m of largest w, ties to the lowest i, or S when C_m is empty;
+ *      second_m = the same over C_m without first_m.  The split pick is (first_0, first_1) if they
+ *      differ, and there is none if both are S.  Otherwise both name one subtask: with
+ *      x = w0[first_0] + w1[second_1] and y = w0[second_0] + w1[first_1] it is (first_0, second_1)
+ *      if x >= y, else (second_0, first_1).  wS = the pick's sum (one f64 add).  This is the argmax
+ *      of w0_i + w1_j over all admissible (i, j), i != j: IEEE addition is monotone in each operand,
+ *      so the rounded sum of the two largest terms is no smaller than any other rounded sum.
+ *      The joint pick iJ = the i in CJ of largest wJ, ties to the lowest i
+ *   6. choose.  The split pick is "full" when both members are < S.
+ *        with OC_TEAM_SPLIT_FIRST and a full split pick: split
+ *        otherwise, if CJ is non-empty and (there is no split pick or wJ[iJ] >= wS): joint
+ *          (cooperative allocations come first in add_subtasks' enumeration)
+ *        otherwise, if there is a split pick: split
+ *        otherwise idle, OC_TEAMF_IDLE
+ *   7. if (cur0, cur1, curJ) differs from its value after step 1: OC_TEAMF_SWITCHED, cnt0 = the
+ *      count of a0's member on `state` (joint: of curJ; None: 0) and cnt1 = the count of a1's
+ *      member (joint or None: 0).  OC_TEAMF_JOINT iff the allocation is joint at exit
+ * ------------------------------------------------------------------------------------- */
+#define OC_TEAM_INIT        1   /* every env below B starts its episode: team state initialised first */
+#define OC_TEAM_COMMIT      2   /* keep the current allocation while all its members are candidates */
+#define OC_TEAM_SPLIT_FIRST 4   /* a full split pick wins over the joint pick whatever their weights */
+#define OC_TEAMF_COMPLETED0 0x01  /* a0's member's count rose: removed from the incomplete set */
+#define OC_TEAMF_COMPLETED1 0x02  /* a1's member's count rose (a joint completion sets both) */
+#define OC_TEAMF_SWITCHED   0x04  /* the allocation at exit differs from the one at entry (after step 1) */
+#define OC_TEAMF_REINIT     0x08  /* team state initialised in this call */
+#define OC_TEAMF_JOINT      0x10  /* the allocation at exit is joint */
+#define OC_TEAMF_IDLE       0x20  /* step 6 found neither a split nor a joint pick */
+#define OC_TEAM_OUT 0xFF          /* a cur plane's byte where the env is not that plane's launch's */
+#define OC_TEAM_MAX_SUBTASKS 21   /* 3 configurations per subtask in the OC_MAX_SUBTASKS staging */
+#define OC_TEAM_PLANES(S) (OC_PROGRESS_EVENT_PLANES(S) + 5)
+
+/*   state, state_prev : as oc_task_select (OC_TEAM_INIT wins over state_prev; with neither, nothing
+ *                  is initialised)
+ *   subtasks     : host array of S rows, 1 <= S <= OC_TEAM_MAX_SUBTASKS; only kind, start_mask and
+ *                  goal_mask are read.  OC_SUB_NONE rows are never candidates
+ *   agents       : host array of 2 agent indices, a0 < a1 < A (so A >= 2)
+ *   tstate       : required, caller-owned, u8 [OC_TEAM_PLANES(S)][pitch], read and written in place
+ *                  (an env's bytes are read before they are written)
+ *   bound        : nullable, f32 [2][pitch], 4-byte aligned: each agent's member's lower bound; the
+ *                  joint bound in both planes for a joint allocation; +0.0f for None
+ *   info         : nullable, u8 [pitch], OC_TEAMF_* bits
+ * Columns >= B of every buffer stay untouched.  Stream-ordered, no allocation, no synchronisation
+ * (hipGraph-capturable, as oc_step).  A bad S, agents or flags, A = 1, a NULL state, subtasks,
+ * agents or tstate, a misaligned bound, or a host-only handle is OC_EINVAL; B = 0 is OK. */
+int oc_team_select(const oc_handle* h, const void* state, const void* state_prev, const oc_subtask* subtasks,
+                   int32_t num_subtasks, const uint8_t* agents, int32_t flags, uint8_t* tstate, float* bound,
+                   uint8_t* info, int64_t B, void* stream);
+
+/* The same on the host (what oc_cpu_step is to oc_step): HOST buffers, works on OC_DEVICE_HOST
+ * handles, the kernel's row function compiled for the host, threaded over env ranges (nthreads
+ * 0 = the host's hardware threads; at least 1,024 rows each).  It never touches the device;
+ * oc_team_select never calls it.  The two agree byte for byte on tstate, bound and info (the f64
+ * division and the one add are IEEE on both sides). */
+int oc_cpu_team_select(const oc_handle* h, const void* state, const void* state_prev, const oc_subtask* subtasks,
+                       int32_t num_subtasks, const uint8_t* agents, int32_t flags, uint8_t* tstate, float* bound,
+                       uint8_t* info, int64_t B, int32_t nthreads);
+
+/* ---------------------------------------------------------------------------------------
  * Per-env Bayesian belief over a watched agent's subtask (additive to ABI 12): Bayesian Delegation's
  * inference step on the batch.  Per env and watched agent a, a posterior over S + 1 hypotheses:
  * hypothesis i < S is "a alone follows subtasks[i]", hypothesis S is "a follows None".
