@@ -557,6 +557,19 @@ struct RollArgs {
     int64_t pitch, B;
 };
 
+// oc_rollout.h's names of the partner rules' flag values are the documented ones
+static_assert(ocro::kTaskCommit == OC_TASK_COMMIT && ocro::kTaskDistinct == OC_TASK_DISTINCT &&
+              ocro::kTaskfCompleted == OC_TASKF_COMPLETED && ocro::kTaskfSwitched == OC_TASKF_SWITCHED &&
+              ocro::kTaskfReinit == OC_TASKF_REINIT, "oc_rollout.h: task_env's flags");
+static_assert(ocro::kTeamCommit == OC_TEAM_COMMIT && ocro::kTeamSplitFirst == OC_TEAM_SPLIT_FIRST &&
+              ocro::kTeamOut == OC_TEAM_OUT && ocro::kTeamfCompleted0 == OC_TEAMF_COMPLETED0 &&
+              ocro::kTeamfCompleted1 == OC_TEAMF_COMPLETED1 && ocro::kTeamfSwitched == OC_TEAMF_SWITCHED &&
+              ocro::kTeamfReinit == OC_TEAMF_REINIT && ocro::kTeamfJoint == OC_TEAMF_JOINT &&
+              ocro::kTeamfIdle == OC_TEAMF_IDLE, "oc_rollout.h: team_env's flags");
+static_assert(ocro::kBelfUpdated == OC_BELF_UPDATED && ocro::kBelfPruned == OC_BELF_PRUNED &&
+              ocro::kBelfReinit == OC_BELF_REINIT && ocro::kBelfReset == OC_BELF_RESET &&
+              ocro::kBelfRaised == OC_BELF_RAISED, "oc_rollout.h: belief_env's flags");
+
 // Stage the level's table blob and the subtask configurations in LDS.
 template <int NT = kBlock>
 __device__ __forceinline__ void stage_roll_tables(const RollArgs& R, const uint8_t* blob_g, uint32_t* blob_w,
@@ -590,6 +603,28 @@ __host__ __device__ __forceinline__ ocro::RowT<K, W> load_row(const uint8_t* __r
         r.mask[j >> 3] |= (uint64_t)sin[(PL::MASK + j) * P + e] << (8 * (j & 7));
     }
     return r;
+}
+
+// The agent-pair table (device memory; L.pair_off), or none: a level without one.
+__device__ __forceinline__ const uint32_t* pair_table_of(const RollArgs& R, const uint8_t* blob_g) {
+    return R.L.pair_off != 0 ? (const uint32_t*)(blob_g + R.L.pair_off) : nullptr;
+}
+
+// A planner kernel's row operations over the staged tables `blob` (LDS) and the level's whole
+// blob `blob_g` (device memory).  pair_table: the bounds read the agent-pair table.
+template <int A, int K, bool W, bool LEAN, bool GD>
+__device__ __forceinline__ ocro::RowOps<A, K, W, LEAN, GD> plan_ops(const RollArgs& R, const uint8_t* blob,
+                                                                    const uint8_t* blob_g, bool pair_table) {
+    ocro::RowOps<A, K, W, LEAN, GD> ops(R.L, blob, GD ? blob_g + R.L.dist_off : blob + R.L.dist_off);  // distances: LDS (narrow), device memory (wide)
+    if (pair_table) ops.PT = pair_table_of(R, blob_g);
+    return ops;
+}
+
+// An env's partner state starts over: the call says so, or state_prev (where given) shows that the
+// env's episode ended.
+template <int A, int K, bool W>
+__host__ __device__ __forceinline__ bool starts_over(bool init_flag, const uint8_t* sprev, int64_t P, int64_t e) {
+    return init_flag || (sprev != nullptr && (sprev[Planes<A, K, W>::F * P + e] & OC_FLAG_DONE) != 0);
 }
 
 // the row's agent and item planes (t and flags are the caller's).  NT: non-temporal stores
@@ -690,8 +725,7 @@ __global__ __launch_bounds__(kRollBlock) void oc_rollout_kernel(RollArgs R, cons
         if (ai < R.nsub) {
             const ocro::Sub& s = subs[ai];
             const int c0 = (in.acts >> (8 * s.agent[0])) & 0xFFu, c1 = s.n == 2 ? (in.acts >> (8 * s.agent[1])) & 0xFFu : ocro::kNoop;
-            ocro::RowOps<A, K, W, false, GD> ops(R.L, blob, GD ? blob_g + R.L.dist_off : blob + R.L.dist_off);  // distances: LDS (narrow), device memory (wide)
-            if (OC_PT_ROLL) ops.PT = R.L.pair_off != 0 ? (const uint32_t*)(blob_g + R.L.pair_off) : nullptr;
+            auto ops = plan_ops<A, K, W, false, GD>(R, blob, blob_g, OC_PT_ROLL);
             f = ops.run(r, s, c0, c1, bound);
         }
         store_row<A, K, W, true>(sout, P, e, r);
@@ -877,7 +911,7 @@ __global__ __launch_bounds__(kRollBlock) void oc_rollout_group_kernel(RollArgs R
         const ocro::Sub& s = subs[ai];
         const int c0 = (acts >> (8 * s.agent[0])) & 0xFFu, c1 = s.n == 2 ? (acts >> (8 * s.agent[1])) & 0xFFu : ocro::kNoop;
         GroupRowOps<G, A, K> ops(R.L, (const uint8_t*)blob_w, q);
-        if (OC_PT_ROLL) ops.PT = R.L.pair_off != 0 ? (const uint32_t*)(blob_g + R.L.pair_off) : nullptr;
+        if (OC_PT_ROLL) ops.PT = pair_table_of(R, blob_g);
         f = ops.run(r, s, c0, c1, bound);
     }
     if (q == 0) {
@@ -931,8 +965,7 @@ __global__ __launch_bounds__(kBlock) void oc_likelihood_kernel(RollArgs R, const
             uint32_t taken = 0;
 #pragma unroll
             for (int a = 0; a < A; ++a) taken |= (uint32_t)taken_p[a * P + e] << (8 * a);
-            ocro::RowOps<A, K, W, true, GD> ops(R.L, blob, GD ? blob_g + R.L.dist_off : blob + R.L.dist_off);  // distances: LDS (narrow), device memory (wide)
-            if (OC_PT_LIK) ops.PT = R.L.pair_off != 0 ? (const uint32_t*)(blob_g + R.L.pair_off) : nullptr;
+            auto ops = plan_ops<A, K, W, true, GD>(R, blob, blob_g, OC_PT_LIK);
             if (s.kind == 0) {
                 f = 0;
                 if (lane == 0) f = ops.likelihood(r, s, taken, self_agent, beta, nap, v);
@@ -1069,8 +1102,7 @@ __global__ __launch_bounds__(kBlock) void oc_policy_kernel(RollArgs R, PolicyArg
             joint = s.n == 2;
             const int ncand = joint ? 25 : 5;
             ocro::RowT<K, W> r = load_row<A, K, W>(sin, P, e);
-            ocro::RowOps<A, K, W, true, GD> ops(R.L, blob, GD ? blob_g + R.L.dist_off : blob + R.L.dist_off);  // distances: LDS (narrow), device memory (wide)
-            if (OC_PT_LIK) ops.PT = R.L.pair_off != 0 ? (const uint32_t*)(blob_g + R.L.pair_off) : nullptr;
+            auto ops = plan_ops<A, K, W, true, GD>(R, blob, blob_g, OC_PT_LIK);
             bool lg = false;    // this lane's candidate is legal
             bool best = false;  // ... and its Q is the row's min (None: it is the mode)
             f = OC_POL_RAISES;
@@ -1235,8 +1267,7 @@ __global__ __launch_bounds__(kBlock) void oc_likelihood_compact_kernel(RollArgs 
                     uint32_t taken = 0;
 #pragma unroll
                     for (int a = 0; a < A; ++a) taken |= (uint32_t)taken_p[a * P + e] << (8 * a);
-                    ocro::RowOps<A, K, W, true, GD> ops(R.L, blob, GD ? blob_g + R.L.dist_off : blob + R.L.dist_off);
-                    if (OC_PT_LIK) ops.PT = R.L.pair_off != 0 ? (const uint32_t*)(blob_g + R.L.pair_off) : nullptr;
+                    auto ops = plan_ops<A, K, W, true, GD>(R, blob, blob_g, OC_PT_LIK);
                     if (s.kind == 0) {
                         f = 0;
                         if (lane == 0) f = ops.likelihood(r, s, taken, self_agent, beta, nap, v);
@@ -1294,8 +1325,7 @@ __global__ __launch_bounds__(kBlock) void oc_likelihood_compact_kernel(RollArgs 
                 const int ai = alloc != nullptr ? alloc[e] : 0;
                 const ocro::Sub& s = subs[ai];
                 ocro::RowT<K, W> r = load_row<A, K, W>(sin, P, e);
-                ocro::RowOps<A, K, W, true, GD> ops(R.L, blob, GD ? blob_g + R.L.dist_off : blob + R.L.dist_off);
-                if (OC_PT_LIK) ops.PT = R.L.pair_off != 0 ? (const uint32_t*)(blob_g + R.L.pair_off) : nullptr;
+                auto ops = plan_ops<A, K, W, true, GD>(R, blob, blob_g, OC_PT_LIK);
                 ops.level0(r, s);
                 const bool joint = s.n == 2;
                 const int a0 = joint ? k / 5 : k, c1 = joint ? k % 5 : ocro::kNoop;
@@ -1376,8 +1406,7 @@ __global__ __launch_bounds__(kBlock) void oc_bounds_kernel(RollArgs R, const uin
     const int i0 = (int)(blockIdx.y * R.nsub / gridDim.y), i1 = (int)((blockIdx.y + 1) * R.nsub / gridDim.y);
     for (int64_t e = blockIdx.x * (int64_t)kBlock + threadIdx.x; e < R.B; e += (int64_t)gridDim.x * kBlock) {
         const ocro::RowT<K, W> r = load_row<A, K, W>(sin, P, e);
-        ocro::RowOps<A, K, W, false, GD> ops(R.L, blob, GD ? blob_g + R.L.dist_off : blob + R.L.dist_off);  // distances: LDS (narrow), device memory (wide)
-        ops.PT = R.L.pair_off != 0 ? (const uint32_t*)(blob_g + R.L.pair_off) : nullptr;  // the agent-pair table (device memory)
+        auto ops = plan_ops<A, K, W, false, GD>(R, blob, blob_g, true);  // the agent-pair table (device memory)
         const auto br = ops.template bound_row<true>(r);  // the row's agent nodes, slot sets: once for its configurations
         for (int i = i0; i < i1; ++i) {
             float v;
@@ -1409,11 +1438,10 @@ __global__ __launch_bounds__(kBlock) void oc_task_kernel(RollArgs R, TaskArgs Q,
     stage_roll_tables(R, blob_g, blob_w, subs);
     const uint8_t* blob = (const uint8_t*)blob_w;
     const int64_t P = R.pitch;
-    using PL = Planes<A, K, W>;
     for (int64_t e = blockIdx.x * (int64_t)kBlock + threadIdx.x; e < R.B; e += (int64_t)gridDim.x * kBlock) {
         const ocro::RowT<K, W> r = load_row<A, K, W>(sin, P, e);
-        const bool init = (Q.flags & OC_TASK_INIT) != 0 || (sprev != nullptr && (sprev[PL::F * P + e] & OC_FLAG_DONE) != 0);
-        ocro::RowOps<A, K, W, false, GD> ops(R.L, blob, GD ? blob_g + R.L.dist_off : blob + R.L.dist_off);  // distances: LDS (narrow), device memory (wide)
+        const bool init = starts_over<A, K, W>((Q.flags & OC_TASK_INIT) != 0, sprev, P, e);
+        auto ops = plan_ops<A, K, W, false, GD>(R, blob, blob_g, false);  // one-agent rows only: no pair table
         ops.task_env(r, subs, Q.S, Q.M, Q.flags, init, ts + e, bound != nullptr ? bound + e : nullptr,
                      info != nullptr ? info + e : nullptr, P);
     }
@@ -1440,12 +1468,10 @@ __global__ __launch_bounds__(kBlock) void oc_team_kernel(RollArgs R, TeamArgs Q,
     stage_roll_tables(R, blob_g, blob_w, subs);
     const uint8_t* blob = (const uint8_t*)blob_w;
     const int64_t P = R.pitch;
-    using PL = Planes<A, K, W>;
     for (int64_t e = blockIdx.x * (int64_t)kBlock + threadIdx.x; e < R.B; e += (int64_t)gridDim.x * kBlock) {
         const ocro::RowT<K, W> r = load_row<A, K, W>(sin, P, e);
-        const bool init = (Q.flags & OC_TEAM_INIT) != 0 || (sprev != nullptr && (sprev[PL::F * P + e] & OC_FLAG_DONE) != 0);
-        ocro::RowOps<A, K, W, false, GD> ops(R.L, blob, GD ? blob_g + R.L.dist_off : blob + R.L.dist_off);  // distances: LDS (narrow), device memory (wide)
-        ops.PT = R.L.pair_off != 0 ? (const uint32_t*)(blob_g + R.L.pair_off) : nullptr;  // the agent-pair table (device memory)
+        const bool init = starts_over<A, K, W>((Q.flags & OC_TEAM_INIT) != 0, sprev, P, e);
+        auto ops = plan_ops<A, K, W, false, GD>(R, blob, blob_g, true);  // the agent-pair table (device memory)
         ops.team_env(r, subs, Q.S, Q.flags, init, ts + e, bound != nullptr ? bound + e : nullptr,
                      info != nullptr ? info + e : nullptr, P);
     }
@@ -1485,7 +1511,6 @@ __global__ __launch_bounds__(kBlock) void oc_belief_kernel(RollArgs R, BeliefArg
     stage_roll_tables(R, blob_g, blob_w, subs);
     const uint8_t* blob = (const uint8_t*)blob_w;
     const int64_t P = R.pitch;
-    using PL = Planes<A, K, W>;
     using Row = ocro::RowT<K, W>;
     const int lane = (int)(threadIdx.x & (G - 1));
     const int S = Q.S, HP = (S + 8) >> 3, EP = (S + 7) >> 3;
@@ -1509,7 +1534,7 @@ __global__ __launch_bounds__(kBlock) void oc_belief_kernel(RollArgs R, BeliefArg
     const int64_t ngroups = (int64_t)gridDim.x * (kBlock / G);
     for (int64_t e = (int64_t)blockIdx.x * (kBlock / G) + threadIdx.x / G; e < R.B; e += ngroups) {
         // group-uniform from here on, except where `lane` is named
-        const bool init = (Q.flags & OC_BELIEF_INIT) != 0 || (sprev[PL::F * P + e] & OC_FLAG_DONE) != 0;
+        const bool init = starts_over<A, K, W>((Q.flags & OC_BELIEF_INIT) != 0, sprev, P, e);
         uint64_t open = 0ull, live = 0ull, ev = 0ull;
         if (!init) {
             for (int c = 0; c < HP; ++c) {
@@ -1547,8 +1572,8 @@ __global__ __launch_bounds__(kBlock) void oc_belief_kernel(RollArgs R, BeliefArg
             const Row r0 = load_row<A, K, W>(sprev, P, e);
             int t = taken[a * P + e];
             t = t > ocro::kNoop ? ocro::kNoop : t;
-            using Ops = ocro::RowOps<A, K, W, true, GD>;
-            Ops ops(R.L, blob, GD ? blob_g + R.L.dist_off : blob + R.L.dist_off);  // distances: LDS (narrow), device memory (wide)
+            auto ops = plan_ops<A, K, W, true, GD>(R, blob, blob_g, false);  // one-agent hypotheses only: no pair table
+            using Ops = decltype(ops);
             const uint32_t mv = ops.none_movable(r0, a);  // the None hypothesis' movable actions, full state
             ops.ac = ops.kNoAc;
             Row v = r0;
@@ -2407,6 +2432,16 @@ static int run_ranges(int64_t nt, Fn&& fn) {
     return OC_OK;
 }
 
+// A host entry point's loop: the call's units (envs, or words of four envs) split into one range
+// per thread of host_threads(nthreads, units, min_units), fn(A, K, BoolC<wide>, u0, u1) for each.
+template <class Fn>
+static int host_ranges(const oc_handle* h, int32_t nthreads, int64_t units, int64_t min_units, Fn&& fn) {
+    const int64_t nt = host_threads(nthreads, units, min_units);
+    return run_ranges(nt, [&](int64_t i) {
+        return dispatch_w(h, [&](auto a, auto k, auto w) { return fn(a, k, w, units * i / nt, units * (i + 1) / nt); });
+    });
+}
+
 // oc_cpu_nav_policy's worker: rows [e0, e1), each the whole-row ocro::RowOps::policy
 template <int A, int K, bool W>
 static void host_policy_range(const RollArgs& R, const PolicyArgs& Q, const uint8_t* blob, const uint8_t* sin,
@@ -2594,7 +2629,9 @@ static int roll_args(const oc_handle* h, const oc_subtask* subtasks, int32_t num
 // by default (graphs of more than ~245 nodes) the kernel must be allowed more, up to the CU's
 // 160 KB; the kernel's static LDS counts against the same limit.
 constexpr int kLdsPerCu = 160 * 1024;
-static int allow_dyn_lds(const void* kernel, int dyn, int static_lds = 16 * 1024) {
+static_assert((8 * kBlock) % kRollBlock == 0, "oc_rollout's grid: whole rollout blocks per CU");
+constexpr int kPlanStaticLds = 16 * 1024;  // an upper bound of a planner kernel's static LDS (the subtask rows)
+static int allow_dyn_lds(const void* kernel, int dyn, int static_lds) {
     // static_lds: an upper bound of the kernel's static LDS; together with `dyn` within the default
     // 64 KB nothing needs to be set
     if (dyn + static_lds <= 64 * 1024) return OC_OK;
@@ -2605,6 +2642,47 @@ static int allow_dyn_lds(const void* kernel, int dyn, int static_lds = 16 * 1024
                     (int)fa.sharedSizeBytes, kLdsPerCu);
     if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, dyn) != hipSuccess)
         return hip_check("hipFuncSetAttribute");
+    return OC_OK;
+}
+
+// One launch of a planner kernel: R's staged tables as its dynamic LDS, R its first argument.
+// what: the launch's name in a HIP error's message.
+template <class Kernel, class... Args>
+static int launch_staged(Kernel kernel, dim3 grid, dim3 block, const RollArgs& R, hipStream_t st, const char* what,
+                         int static_lds, Args... args) {
+    if (const int rc = allow_dyn_lds((const void*)kernel, R.blob_words * 4, static_lds)) return rc;
+    hipLaunchKernelGGL(kernel, grid, block, R.blob_words * 4, st, R, args...);
+    return hip_check(what);
+}
+
+// Blocks of a launch over B envs, rows_per_block each: one round of blocks, at most blocks_per_cu
+// per CU (the kernels stride over the rest).
+static unsigned env_grid(const oc_handle* h, int64_t B, int64_t rows_per_block, int64_t blocks_per_cu) {
+    const int64_t need = (B + rows_per_block - 1) / rows_per_block, cap = (int64_t)h->cus * blocks_per_cu;
+    return (unsigned)(need < cap ? need : cap);
+}
+
+// The one- (a1 < 0) or two-agent Level-0 row of a partner entry point's subtask `src`.
+static oc_subtask level0_row(const oc_subtask& src, int a0, int a1 = -1) {
+    oc_subtask d{};
+    d.kind = src.kind;
+    d.num_agents = a1 < 0 ? 1 : 2;
+    d.agent[0] = (uint8_t)a0;
+    if (a1 >= 0) d.agent[1] = (uint8_t)a1;
+    d.start_mask[0] = src.start_mask[0];
+    d.start_mask[1] = src.start_mask[1];
+    d.goal_mask = src.goal_mask;
+    d.level = OC_LEVEL0;
+    return d;
+}
+
+// A partner entry point's agent list: M distinct agents below A.  what: the message's prefix.
+static int check_agents(const char* what, const uint8_t* agents, int M, int A) {
+    for (int m = 0; m < M; ++m) {
+        if (agents[m] >= A) return fail(OC_EINVAL, "%s: agent %d", what, agents[m]);
+        for (int q = 0; q < m; ++q)
+            if (agents[q] == agents[m]) return fail(OC_EINVAL, "%s: agent %d listed twice", what, agents[m]);
+    }
     return OC_OK;
 }
 
@@ -3097,26 +3175,21 @@ int oc_rollout(const oc_handle* h, const void* state_in, void* state_out, const 
     RollArgs R;
     if (const int rc = roll_args(h, subtasks, num_subtasks, B, R, true)) return rc;
     if (B == 0) return OC_OK;
-    const int64_t need = (B + kRollBlock - 1) / kRollBlock, cap = (int64_t)h->cus * 8 * kBlock / kRollBlock;
-    const dim3 grid((unsigned)(need < cap ? need : cap));
+    const dim3 grid(env_grid(h, B, kRollBlock, 8 * kBlock / kRollBlock));
     hipStream_t st = (hipStream_t)stream;
     if (!h->wide && !h->roll.dist_global && B * kRollGroup <= (int64_t)h->cus * kRollBlock) {
         // one round of blocks with a lane group per row (oc_rollout_group_kernel)
         const dim3 ggrid((unsigned)((B * kRollGroup + kRollBlock - 1) / kRollBlock));
         return dispatch_ak(h->A, h->K, [&](auto a, auto k) {
-            const auto kernel = oc_rollout_group_kernel<a(), k()>;
-            if (const int rc = allow_dyn_lds((const void*)kernel, R.blob_words * 4)) return rc;
-            hipLaunchKernelGGL(kernel, ggrid, dim3(kRollBlock), R.blob_words * 4, st, R, (const uint8_t*)state_in,
-                               (uint8_t*)state_out, actions, alloc, h->roll_blob, out_flags, lower_bound);
-            return hip_check("oc_rollout launch");
+            return launch_staged(oc_rollout_group_kernel<a(), k()>, ggrid, dim3(kRollBlock), R, st, "oc_rollout launch",
+                                 kPlanStaticLds, (const uint8_t*)state_in, (uint8_t*)state_out, actions, alloc,
+                                 (const uint8_t*)h->roll_blob, out_flags, lower_bound);
         });
     }
     return dispatch_plan(h, [&](auto a, auto k, auto w, auto gd) {
-        const auto kernel = oc_rollout_kernel<a(), k(), w(), gd()>;
-        if (const int rc = allow_dyn_lds((const void*)kernel, R.blob_words * 4)) return rc;
-        hipLaunchKernelGGL(kernel, grid, dim3(kRollBlock), R.blob_words * 4, st, R, (const uint8_t*)state_in,
-                           (uint8_t*)state_out, actions, alloc, h->roll_blob, out_flags, lower_bound);
-        return hip_check("oc_rollout launch");
+        return launch_staged(oc_rollout_kernel<a(), k(), w(), gd()>, grid, dim3(kRollBlock), R, st, "oc_rollout launch",
+                             kPlanStaticLds, (const uint8_t*)state_in, (uint8_t*)state_out, actions, alloc,
+                             (const uint8_t*)h->roll_blob, out_flags, lower_bound);
     });
 }
 
@@ -3144,15 +3217,13 @@ int oc_nav_likelihood(const oc_handle* h, const void* state, const uint8_t* take
     const bool compact = OC_LIK_COMPACT && h->lik_form == OC_LIK_FORM_AUTO &&
                          h->roll.lds_bytes + kLikCompactLds + (int)sizeof(ocro::Sub) * OC_MAX_SUBTASKS <= kLdsPerCu;
     const int64_t rows_per_block = compact ? (kBlock / 64) * lik_rows_per_round((int)G) : kBlock / G;
-    const int64_t need = (B + rows_per_block - 1) / rows_per_block, cap = (int64_t)h->cus * (any_joint ? 16 : 8);
-    const dim3 grid((unsigned)(need < cap ? need : cap));
+    const dim3 grid(env_grid(h, B, rows_per_block, any_joint ? 16 : 8));
     hipStream_t st = (hipStream_t)stream;
     return dispatch_plan(h, [&](auto a, auto k, auto w, auto gd) {
         auto go = [&](auto kernel) {
-            if (const int rc = allow_dyn_lds((const void*)kernel, R.blob_words * 4)) return rc;
-            hipLaunchKernelGGL(kernel, grid, dim3(kBlock), R.blob_words * 4, st, R, (const uint8_t*)state, taken, alloc,
-                               h->roll_blob, self_agent, beta, none_action_prob, likelihood, out_flags);
-            return hip_check("oc_nav_likelihood launch");
+            return launch_staged(kernel, grid, dim3(kBlock), R, st, "oc_nav_likelihood launch", kPlanStaticLds,
+                                 (const uint8_t*)state, taken, alloc, (const uint8_t*)h->roll_blob, (int)self_agent, beta,
+                                 none_action_prob, likelihood, out_flags);
         };
         if (compact && any_joint) return go(oc_likelihood_compact_kernel<a(), k(), 32, w(), gd()>);
         if (compact) return go(oc_likelihood_compact_kernel<a(), k(), 8, w(), gd()>);
@@ -3204,15 +3275,12 @@ int oc_nav_policy(const oc_handle* h, const void* state, const uint8_t* alloc, c
     // the grouped likelihood's grid: a lane group per row, up to 16 blocks per CU with 32-lane
     // groups, 8 with 8-lane groups
     const int64_t rows_per_block = kBlock / (any_joint ? 32 : 8);
-    const int64_t need = (B + rows_per_block - 1) / rows_per_block, cap = (int64_t)h->cus * (any_joint ? 16 : 8);
-    const dim3 grid((unsigned)(need < cap ? need : cap));
+    const dim3 grid(env_grid(h, B, rows_per_block, any_joint ? 16 : 8));
     hipStream_t st = (hipStream_t)stream;
     return dispatch_plan(h, [&](auto a, auto k, auto w, auto gd) {
         auto go = [&](auto kernel) {
-            if (const int rc = allow_dyn_lds((const void*)kernel, R.blob_words * 4)) return rc;
-            hipLaunchKernelGGL(kernel, grid, dim3(kBlock), R.blob_words * 4, st, R, Q, (const uint8_t*)state, alloc,
-                               h->roll_blob, actions, probs, out_flags);
-            return hip_check("oc_nav_policy launch");
+            return launch_staged(kernel, grid, dim3(kBlock), R, st, "oc_nav_policy launch", kPlanStaticLds, Q,
+                                 (const uint8_t*)state, alloc, (const uint8_t*)h->roll_blob, actions, probs, out_flags);
         };
         if (any_joint) return go(oc_policy_kernel<a(), k(), 32, w(), gd()>);
         return go(oc_policy_kernel<a(), k(), 8, w(), gd()>);
@@ -3232,14 +3300,11 @@ int oc_cpu_nav_policy(const oc_handle* h, const void* state, const uint8_t* allo
                                    actions, probs, num_cand, out_flags, B, true, R, Q, any_joint))
         return rc;
     if (B == 0) return OC_OK;
-    const int64_t nt = host_threads(nthreads, B, 1024);  // >= 1,024 rows (up to 25 rollouts each) per thread
     const uint8_t* blob = h->roll_blob_host.data();
-    return run_ranges(nt, [&](int64_t i) {
-        const int64_t e0 = B * i / nt, e1 = B * (i + 1) / nt;
-        return dispatch_w(h, [&](auto a, auto k, auto w) {
-            host_policy_range<a(), k(), w()>(R, Q, blob, (const uint8_t*)state, alloc, actions, probs, out_flags, e0, e1);
-            return OC_OK;
-        });
+    // >= 1,024 rows (up to 25 rollouts each) per thread
+    return host_ranges(h, nthreads, B, 1024, [&](auto a, auto k, auto w, int64_t e0, int64_t e1) {
+        host_policy_range<a(), k(), w()>(R, Q, blob, (const uint8_t*)state, alloc, actions, probs, out_flags, e0, e1);
+        return OC_OK;
     });
 }
 
@@ -3260,8 +3325,7 @@ int oc_subtask_bounds(const oc_handle* h, const void* state, const oc_subtask* s
     RollArgs R;
     if (const int rc = roll_args(h, subtasks, num_subtasks, B, R)) return rc;
     if (B == 0) return OC_OK;
-    const int64_t need = (B + kBlock - 1) / kBlock, cap = (int64_t)h->cus * 8;
-    const int64_t bx = need < cap ? need : cap;
+    const int64_t bx = env_grid(h, B, kBlock, 8);
     // configuration chunks: enough blocks for OC_BOUNDS_BLOCKS_PER_CU per CU, at most one
     // configuration per chunk (round 2, C5, 2^18 envs x 64 configurations: 0.75 ms unchunked,
     // 0.53 / 0.46 / 0.44 / 0.44 ms at 16 / 32 / 64 / 128 blocks per CU, 0.47 ms at one
@@ -3272,11 +3336,8 @@ int oc_subtask_bounds(const oc_handle* h, const void* state, const oc_subtask* s
     const dim3 grid((unsigned)bx, (unsigned)chunks);
     hipStream_t st = (hipStream_t)stream;
     return dispatch_plan(h, [&](auto a, auto k, auto w, auto gd) {
-        const auto kernel = oc_bounds_kernel<a(), k(), w(), gd()>;
-        if (const int rc = allow_dyn_lds((const void*)kernel, R.blob_words * 4)) return rc;
-        hipLaunchKernelGGL(kernel, grid, dim3(kBlock), R.blob_words * 4, st, R, (const uint8_t*)state, h->roll_blob,
-                           lower_bound, doable);
-        return hip_check("oc_subtask_bounds launch");
+        return launch_staged(oc_bounds_kernel<a(), k(), w(), gd()>, grid, dim3(kBlock), R, st, "oc_subtask_bounds launch",
+                             kPlanStaticLds, (const uint8_t*)state, (const uint8_t*)h->roll_blob, lower_bound, doable);
     });
 }
 
@@ -3295,25 +3356,11 @@ static int task_args(const oc_handle* h, const void* state, const oc_subtask* su
         return fail(OC_EINVAL, "task_select: num_scripted x num_subtasks = %d (at most %d)", M * S, OC_MAX_SUBTASKS);
     if (flags < 0 || flags > (OC_TASK_INIT | OC_TASK_COMMIT | OC_TASK_DISTINCT))
         return fail(OC_EINVAL, "task_select: flags %d", flags);
-    for (int m = 0; m < M; ++m) {
-        if (agents[m] >= h->A) return fail(OC_EINVAL, "task_select: agent %d", agents[m]);
-        for (int q = 0; q < m; ++q)
-            if (agents[q] == agents[m]) return fail(OC_EINVAL, "task_select: agent %d listed twice", agents[m]);
-    }
+    if (const int rc = check_agents("task_select", agents, M, h->A)) return rc;
     if (((uintptr_t)bound & 3u) || ((uintptr_t)state & 1u)) return fail(OC_EINVAL, "task_select: misaligned buffer");
     oc_subtask rows[OC_MAX_SUBTASKS];
     for (int m = 0; m < M; ++m)
-        for (int i = 0; i < S; ++i) {
-            oc_subtask& d = rows[m * S + i];
-            d = oc_subtask{};
-            d.kind = subtasks[i].kind;
-            d.num_agents = 1;
-            d.agent[0] = agents[m];
-            d.start_mask[0] = subtasks[i].start_mask[0];
-            d.start_mask[1] = subtasks[i].start_mask[1];
-            d.goal_mask = subtasks[i].goal_mask;
-            d.level = OC_LEVEL0;
-        }
+        for (int i = 0; i < S; ++i) rows[m * S + i] = level0_row(subtasks[i], agents[m]);
     if (const int rc = roll_args(h, rows, M * S, B, R, false, host)) return rc;
     Q.S = S;
     Q.M = M;
@@ -3332,15 +3379,12 @@ int oc_task_select(const oc_handle* h, const void* state, const void* state_prev
     if (const int rc = task_args(h, state, subtasks, num_subtasks, agents, num_scripted, flags, tstate, bound, B, false, R, Q))
         return rc;
     if (B == 0) return OC_OK;
-    const int64_t need = (B + kBlock - 1) / kBlock, cap = (int64_t)h->cus * 8;
-    const dim3 grid((unsigned)(need < cap ? need : cap));
+    const dim3 grid(env_grid(h, B, kBlock, 8));
     hipStream_t st = (hipStream_t)stream;
     return dispatch_plan(h, [&](auto a, auto k, auto w, auto gd) {
-        const auto kernel = oc_task_kernel<a(), k(), w(), gd()>;
-        if (const int rc = allow_dyn_lds((const void*)kernel, R.blob_words * 4)) return rc;
-        hipLaunchKernelGGL(kernel, grid, dim3(kBlock), R.blob_words * 4, st, R, Q, (const uint8_t*)state,
-                           (const uint8_t*)state_prev, h->roll_blob, tstate, bound, info);
-        return hip_check("oc_task_select launch");
+        return launch_staged(oc_task_kernel<a(), k(), w(), gd()>, grid, dim3(kBlock), R, st, "oc_task_select launch",
+                             kPlanStaticLds, Q, (const uint8_t*)state, (const uint8_t*)state_prev,
+                             (const uint8_t*)h->roll_blob, tstate, bound, info);
     });
 }
 
@@ -3354,22 +3398,18 @@ int oc_cpu_task_select(const oc_handle* h, const void* state, const void* state_
     if (const int rc = task_args(h, state, subtasks, num_subtasks, agents, num_scripted, flags, tstate, bound, B, true, R, Q))
         return rc;
     if (B == 0) return OC_OK;
-    const int64_t nt = host_threads(nthreads, B, 1024);  // >= 1,024 rows (up to M x S bound walks each) per thread
     const uint8_t* blob = h->roll_blob_host.data();
     const uint8_t *sin = (const uint8_t*)state, *sprev = (const uint8_t*)state_prev;
-    return run_ranges(nt, [&](int64_t i) {
-        const int64_t e0 = B * i / nt, e1 = B * (i + 1) / nt;
-        return dispatch_w(h, [&](auto a, auto k, auto w) {
-            using PL = Planes<a(), k(), w()>;
-            const int64_t P = R.pitch;
-            for (int64_t e = e0; e < e1; ++e) {
-                const bool init = (Q.flags & OC_TASK_INIT) != 0 || (sprev != nullptr && (sprev[PL::F * P + e] & OC_FLAG_DONE) != 0);
-                ocro::RowOps<a(), k(), w(), false, true> ops(R.L, blob);
-                ops.task_env(load_row<a(), k(), w()>(sin, P, e), R.subs, Q.S, Q.M, Q.flags, init, tstate + e,
-                             bound != nullptr ? bound + e : nullptr, info != nullptr ? info + e : nullptr, P);
-            }
-            return OC_OK;
-        });
+    // >= 1,024 rows (up to M x S bound walks each) per thread
+    return host_ranges(h, nthreads, B, 1024, [&](auto a, auto k, auto w, int64_t e0, int64_t e1) {
+        const int64_t P = R.pitch;
+        for (int64_t e = e0; e < e1; ++e) {
+            const bool init = starts_over<a(), k(), w()>((Q.flags & OC_TASK_INIT) != 0, sprev, P, e);
+            ocro::RowOps<a(), k(), w(), false, true> ops(R.L, blob);
+            ops.task_env(load_row<a(), k(), w()>(sin, P, e), R.subs, Q.S, Q.M, Q.flags, init, tstate + e,
+                         bound != nullptr ? bound + e : nullptr, info != nullptr ? info + e : nullptr, P);
+        }
+        return OC_OK;
     });
 }
 
@@ -3396,16 +3436,8 @@ static int team_args(const oc_handle* h, const void* state, const oc_subtask* su
     oc_subtask rows[OC_MAX_SUBTASKS];
     for (int c = 0; c < 3; ++c)
         for (int i = 0; i < S; ++i) {
-            oc_subtask& d = rows[c * S + i];
-            d = oc_subtask{};
-            d.kind = subtasks[i].kind;
-            d.num_agents = c == 2 && d.kind != OC_SUB_NONE ? 2 : 1;  // a None row is a one-agent row and never a candidate
-            d.agent[0] = agents[c == 1 ? 1 : 0];
-            if (d.num_agents == 2) d.agent[1] = agents[1];
-            d.start_mask[0] = subtasks[i].start_mask[0];
-            d.start_mask[1] = subtasks[i].start_mask[1];
-            d.goal_mask = subtasks[i].goal_mask;
-            d.level = OC_LEVEL0;
+            const bool two = c == 2 && subtasks[i].kind != OC_SUB_NONE;  // a None row is a one-agent row and never a candidate
+            rows[c * S + i] = two ? level0_row(subtasks[i], agents[0], agents[1]) : level0_row(subtasks[i], agents[c == 1 ? 1 : 0]);
         }
     if (const int rc = roll_args(h, rows, 3 * S, B, R, false, host)) return rc;
     Q.S = S;
@@ -3423,18 +3455,15 @@ int oc_team_select(const oc_handle* h, const void* state, const void* state_prev
     TeamArgs Q;
     if (const int rc = team_args(h, state, subtasks, num_subtasks, agents, flags, tstate, bound, B, false, R, Q)) return rc;
     if (B == 0) return OC_OK;
-    const int64_t need = (B + kBlock - 1) / kBlock, cap = (int64_t)h->cus * 8;
-    const dim3 grid((unsigned)(need < cap ? need : cap));
+    const dim3 grid(env_grid(h, B, kBlock, 8));
     hipStream_t st = (hipStream_t)stream;
     return dispatch_plan(h, [&](auto a, auto k, auto w, auto gd) {
         if constexpr (decltype(a)::value < 2) {
             return fail(OC_EINVAL, "team_select: a team needs 2 agents");
         } else {
-            const auto kernel = oc_team_kernel<a(), k(), w(), gd()>;
-            if (const int rc = allow_dyn_lds((const void*)kernel, R.blob_words * 4)) return rc;
-            hipLaunchKernelGGL(kernel, grid, dim3(kBlock), R.blob_words * 4, st, R, Q, (const uint8_t*)state,
-                               (const uint8_t*)state_prev, h->roll_blob, tstate, bound, info);
-            return hip_check("oc_team_select launch");
+            return launch_staged(oc_team_kernel<a(), k(), w(), gd()>, grid, dim3(kBlock), R, st, "oc_team_select launch",
+                                 kPlanStaticLds, Q, (const uint8_t*)state, (const uint8_t*)state_prev,
+                                 (const uint8_t*)h->roll_blob, tstate, bound, info);
         }
     });
 }
@@ -3448,26 +3477,22 @@ int oc_cpu_team_select(const oc_handle* h, const void* state, const void* state_
     TeamArgs Q;
     if (const int rc = team_args(h, state, subtasks, num_subtasks, agents, flags, tstate, bound, B, true, R, Q)) return rc;
     if (B == 0) return OC_OK;
-    const int64_t nt = host_threads(nthreads, B, 1024);  // >= 1,024 rows (up to 3 x S bound walks each) per thread
     const uint8_t* blob = h->roll_blob_host.data();
     const uint8_t *sin = (const uint8_t*)state, *sprev = (const uint8_t*)state_prev;
-    return run_ranges(nt, [&](int64_t i) {
-        const int64_t e0 = B * i / nt, e1 = B * (i + 1) / nt;
-        return dispatch_w(h, [&](auto a, auto k, auto w) {
-            if constexpr (decltype(a)::value < 2) {
-                return fail(OC_EINVAL, "team_select: a team needs 2 agents");
-            } else {
-                using PL = Planes<a(), k(), w()>;
-                const int64_t P = R.pitch;
-                for (int64_t e = e0; e < e1; ++e) {
-                    const bool init = (Q.flags & OC_TEAM_INIT) != 0 || (sprev != nullptr && (sprev[PL::F * P + e] & OC_FLAG_DONE) != 0);
-                    ocro::RowOps<a(), k(), w(), false, true> ops(R.L, blob);
-                    ops.team_env(load_row<a(), k(), w()>(sin, P, e), R.subs, Q.S, Q.flags, init, tstate + e,
-                                 bound != nullptr ? bound + e : nullptr, info != nullptr ? info + e : nullptr, P);
-                }
-                return OC_OK;
+    // >= 1,024 rows (up to 3 x S bound walks each) per thread
+    return host_ranges(h, nthreads, B, 1024, [&](auto a, auto k, auto w, int64_t e0, int64_t e1) {
+        if constexpr (decltype(a)::value < 2) {
+            return fail(OC_EINVAL, "team_select: a team needs 2 agents");
+        } else {
+            const int64_t P = R.pitch;
+            for (int64_t e = e0; e < e1; ++e) {
+                const bool init = starts_over<a(), k(), w()>((Q.flags & OC_TEAM_INIT) != 0, sprev, P, e);
+                ocro::RowOps<a(), k(), w(), false, true> ops(R.L, blob);
+                ops.team_env(load_row<a(), k(), w()>(sin, P, e), R.subs, Q.S, Q.flags, init, tstate + e,
+                             bound != nullptr ? bound + e : nullptr, info != nullptr ? info + e : nullptr, P);
             }
-        });
+            return OC_OK;
+        }
     });
 }
 
@@ -3489,24 +3514,10 @@ static int belief_args(const oc_handle* h, const void* state_prev, const uint8_t
         return fail(OC_EINVAL, "belief_update: state_prev and taken are required without OC_BELIEF_INIT");
     if (!(beta == beta) || !(nap >= 0.0 && nap <= 1.0))
         return fail(OC_EINVAL, "belief_update: beta %g, none_action_prob %g", beta, nap);
-    for (int m = 0; m < M; ++m) {
-        if (agents[m] >= h->A) return fail(OC_EINVAL, "belief_update: agent %d", agents[m]);
-        for (int q = 0; q < m; ++q)
-            if (agents[q] == agents[m]) return fail(OC_EINVAL, "belief_update: agent %d listed twice", agents[m]);
-    }
+    if (const int rc = check_agents("belief_update", agents, M, h->A)) return rc;
     if (((uintptr_t)belief & 7u) || ((uintptr_t)state_prev & 1u)) return fail(OC_EINVAL, "belief_update: misaligned buffer");
     oc_subtask rows[OC_MAX_SUBTASKS];
-    for (int i = 0; i < S; ++i) {
-        oc_subtask& d = rows[i];
-        d = oc_subtask{};
-        d.kind = subtasks[i].kind;
-        d.num_agents = 1;
-        d.agent[0] = 0;
-        d.start_mask[0] = subtasks[i].start_mask[0];
-        d.start_mask[1] = subtasks[i].start_mask[1];
-        d.goal_mask = subtasks[i].goal_mask;
-        d.level = OC_LEVEL0;
-    }
+    for (int i = 0; i < S; ++i) rows[i] = level0_row(subtasks[i], 0);
     if (const int rc = roll_args(h, rows, S, B, R, false, host)) return rc;
     Q.beta = beta;
     Q.nap = nap;
@@ -3531,16 +3542,12 @@ int oc_belief_update(const oc_handle* h, const void* state_prev, const uint8_t* 
         return rc;
     if (B == 0) return OC_OK;
     // oc_nav_policy's grid for 8-lane groups, once per watched agent
-    const int64_t rows_per_block = kBlock / 8;
-    const int64_t need = (B + rows_per_block - 1) / rows_per_block, cap = (int64_t)h->cus * 8;
-    const dim3 grid((unsigned)(need < cap ? need : cap), (unsigned)Q.M);
+    const dim3 grid(env_grid(h, B, kBlock / 8, 8), (unsigned)Q.M);
     hipStream_t st = (hipStream_t)stream;
     return dispatch_plan(h, [&](auto a, auto k, auto w, auto gd) {
-        const auto kernel = oc_belief_kernel<a(), k(), w(), gd()>;
-        if (const int rc = allow_dyn_lds((const void*)kernel, R.blob_words * 4, kBeliefStaticLds)) return rc;
-        hipLaunchKernelGGL(kernel, grid, dim3(kBlock), R.blob_words * 4, st, R, Q, (const uint8_t*)state_prev, taken,
-                           events, h->roll_blob, belief, bstate, map, info);
-        return hip_check("oc_belief_update launch");
+        return launch_staged(oc_belief_kernel<a(), k(), w(), gd()>, grid, dim3(kBlock), R, st, "oc_belief_update launch",
+                             kBeliefStaticLds, Q, (const uint8_t*)state_prev, taken, events, (const uint8_t*)h->roll_blob,
+                             belief, bstate, map, info);
     });
 }
 
@@ -3556,33 +3563,29 @@ int oc_cpu_belief_update(const oc_handle* h, const void* state_prev, const uint8
                                    none_action_prob, flags, belief, bstate, B, true, R, Q))
         return rc;
     if (B == 0) return OC_OK;
-    const int64_t nt = host_threads(nthreads, B, 1024);  // >= 1,024 rows (M x S hypotheses each) per thread
     const uint8_t* blob = h->roll_blob_host.data();
     const uint8_t* sprev = (const uint8_t*)state_prev;
-    return run_ranges(nt, [&](int64_t i) {
-        const int64_t e0 = B * i / nt, e1 = B * (i + 1) / nt;
-        return dispatch_w(h, [&](auto a, auto k, auto w) {
-            using PL = Planes<a(), k(), w()>;
-            using Row = ocro::RowT<k(), w()>;
-            const int64_t P = R.pitch;
-            const int S = Q.S, HP = (S + 8) >> 3, EP = (S + 7) >> 3;
-            for (int64_t e = e0; e < e1; ++e) {
-                const bool init = (Q.flags & OC_BELIEF_INIT) != 0 || (sprev[PL::F * P + e] & OC_FLAG_DONE) != 0;
-                uint64_t ev = 0ull;
-                if (!init && events != nullptr)
-                    for (int c = 0; c < EP; ++c) ev |= (uint64_t)events[c * P + e] << (8 * c);
-                const Row r0 = init ? Row{} : load_row<a(), k(), w()>(sprev, P, e);
-                for (int m = 0; m < Q.M; ++m) {
-                    const int ag = Q.agents[m];
-                    ocro::RowOps<a(), k(), w(), true, true> ops(R.L, blob);
-                    ops.belief_env(r0, R.subs, S, ag, init ? ocro::kNoop : (int)taken[ag * P + e], ev, init, Q.beta, Q.nap,
-                                   belief + (int64_t)m * (S + 1) * P + e, bstate + (int64_t)m * 2 * HP * P + e,
-                                   map != nullptr ? map + m * P + e : nullptr, info != nullptr ? info + m * P + e : nullptr,
-                                   P);
-                }
+    // >= 1,024 rows (M x S hypotheses each) per thread
+    return host_ranges(h, nthreads, B, 1024, [&](auto a, auto k, auto w, int64_t e0, int64_t e1) {
+        using Row = ocro::RowT<k(), w()>;
+        const int64_t P = R.pitch;
+        const int S = Q.S, HP = (S + 8) >> 3, EP = (S + 7) >> 3;
+        for (int64_t e = e0; e < e1; ++e) {
+            const bool init = starts_over<a(), k(), w()>((Q.flags & OC_BELIEF_INIT) != 0, sprev, P, e);
+            uint64_t ev = 0ull;
+            if (!init && events != nullptr)
+                for (int c = 0; c < EP; ++c) ev |= (uint64_t)events[c * P + e] << (8 * c);
+            const Row r0 = init ? Row{} : load_row<a(), k(), w()>(sprev, P, e);
+            for (int m = 0; m < Q.M; ++m) {
+                const int ag = Q.agents[m];
+                ocro::RowOps<a(), k(), w(), true, true> ops(R.L, blob);
+                ops.belief_env(r0, R.subs, S, ag, init ? ocro::kNoop : (int)taken[ag * P + e], ev, init, Q.beta, Q.nap,
+                               belief + (int64_t)m * (S + 1) * P + e, bstate + (int64_t)m * 2 * HP * P + e,
+                               map != nullptr ? map + m * P + e : nullptr, info != nullptr ? info + m * P + e : nullptr,
+                               P);
             }
-            return OC_OK;
-        });
+        }
+        return OC_OK;
     });
 }
 
@@ -3689,16 +3692,13 @@ int oc_cpu_observe(const oc_handle* h, const void* state, void* obs, uint8_t* ac
     ocob::ObsArgs R;
     if (const int rc = observe_args(h, state, obs, action_mask, dtype, view_agent, B, R)) return rc;
     if (B == 0) return OC_OK;
-    const int64_t nt = host_threads(nthreads, B, 16384);  // >= 16 Ki envs per thread
     const uint8_t* tab = h->obs_tab_host.data();
     const uint16_t* statics = (const uint16_t*)(tab + h->obs_static_off);
-    return run_ranges(nt, [&](int64_t i) {
-        const int64_t e0 = B * i / nt, e1 = B * (i + 1) / nt;
-        return dispatch_w(h, [&](auto a, auto k, auto w) {
-            ocob::cpu_observe_range<a(), k(), w()>(R, tab, statics, (const uint8_t*)state, obs, action_mask,
-                                                   dtype == OC_OBS_F16, e0, e1);
-            return OC_OK;
-        });
+    // >= 16 Ki envs per thread
+    return host_ranges(h, nthreads, B, 16384, [&](auto a, auto k, auto w, int64_t e0, int64_t e1) {
+        ocob::cpu_observe_range<a(), k(), w()>(R, tab, statics, (const uint8_t*)state, obs, action_mask,
+                                               dtype == OC_OBS_F16, e0, e1);
+        return OC_OK;
     });
 }
 
@@ -3733,17 +3733,14 @@ int oc_cpu_progress(const oc_handle* h, const void* state_prev, const void* stat
     if (const int rc = progress_args(h, state_prev, states, n, subtasks, num_subtasks, weights, counts, events, reward, B, R))
         return rc;
     if (B == 0) return OC_OK;
-    const int64_t nt = host_threads(nthreads, B, 16384);  // >= 16 Ki envs per thread
     uint8_t tab[ocpg::kTableBytes];
     ocpg::build_table(h->obs_tab_host.data(), R.tile_words, tab);
     const int64_t words = (B + 3) / 4;
-    return run_ranges(nt, [&](int64_t i) {
-        const int64_t g0 = words * i / nt, g1 = words * (i + 1) / nt;
-        return dispatch_w(h, [&](auto a, auto k, auto w) {
-            ocpg::cpu_progress_words<a(), k(), w()>(R, tab, (const uint8_t*)state_prev, (const uint8_t*)states, counts,
-                                                    events, reward, g0, g1);
-            return OC_OK;
-        });
+    // >= 16 Ki envs per thread: 4,096 words of four (ceil(ceil(B / 4) / 4096) = ceil(B / 16384))
+    return host_ranges(h, nthreads, words, 4096, [&](auto a, auto k, auto w, int64_t g0, int64_t g1) {
+        ocpg::cpu_progress_words<a(), k(), w()>(R, tab, (const uint8_t*)state_prev, (const uint8_t*)states, counts,
+                                                events, reward, g0, g1);
+        return OC_OK;
     });
 }
 
@@ -3802,14 +3799,11 @@ int oc_cpu_reset_random(const oc_handle* h, void* state, const void* state_prev,
     if (const int rc = start_args(h, state, B, env_offset, seed, round, what, state_prev != nullptr, R)) return rc;
     if (B == 0) return OC_OK;
     const int64_t words = (B + kEPL - 1) / kEPL;
-    const int64_t nt = host_threads(nthreads, words, 4096);  // >= 4096 words (16 Ki envs) per thread
-    return run_ranges(nt, [&](int64_t i) {
-        const int64_t g0 = words * i / nt, g1 = words * (i + 1) / nt;
-        return dispatch_w(h, [&](auto a, auto k, auto w) {
-            ocsd::host_start_range<a(), k(), w()>(h->args.sw, R, h->start_tab_host.data(), (uint8_t*)state,
-                                                  (const uint8_t*)state_prev, g0, g1);
-            return OC_OK;
-        });
+    // >= 4096 words (16 Ki envs) per thread
+    return host_ranges(h, nthreads, words, 4096, [&](auto a, auto k, auto w, int64_t g0, int64_t g1) {
+        ocsd::host_start_range<a(), k(), w()>(h->args.sw, R, h->start_tab_host.data(), (uint8_t*)state,
+                                              (const uint8_t*)state_prev, g0, g1);
+        return OC_OK;
     });
 }
 

@@ -64,6 +64,15 @@ constexpr uint8_t kNone = 0xFF;
 constexpr uint16_t kNoNode = 0xFFFF;
 constexpr int kFloor = 0, kCounter = 1, kCutboard = 2, kDelivery = 3;  // OC_TILE_*
 constexpr int kNoop = 4;
+// The partner rules' flag values: the OC_TASK_*, OC_TASKF_*, OC_TEAM_*, OC_TEAMF_* and OC_BELF_*
+// macros of include/oc_engine.h under this header's own names (it stands alone; oc_engine.hip,
+// which includes both, asserts that each pair agrees).
+constexpr int kTaskCommit = 2, kTaskDistinct = 4;
+constexpr int kTaskfCompleted = 0x01, kTaskfSwitched = 0x02, kTaskfReinit = 0x04;
+constexpr int kTeamCommit = 2, kTeamSplitFirst = 4, kTeamOut = 0xFF;
+constexpr int kTeamfCompleted0 = 0x01, kTeamfCompleted1 = 0x02, kTeamfSwitched = 0x04, kTeamfReinit = 0x08,
+              kTeamfJoint = 0x10, kTeamfIdle = 0x20;
+constexpr int kBelfUpdated = 0x01, kBelfPruned = 0x02, kBelfReinit = 0x04, kBelfReset = 0x08, kBelfRaised = 0x10;
 constexpr int kDX[5] = {0, 0, -1, 1, 0}, kDY[5] = {1, -1, 0, 0, 0};  // World.NAV_ACTIONS + (0, 0)
 
 // Static level tables, one byte blob (offsets in RollLevel, set by build_roll_level):
@@ -1378,7 +1387,7 @@ struct RowOps {
                 inc = (1ull << S) - 1ull;
                 cur = S;
                 cnt = 0;
-                fl = 4;  // OC_TASKF_REINIT
+                fl = kTaskfReinit;
             }
             const int entry = cur;
             // refresh: the current subtask's count rose (evaluated on every lane, used where cur < S)
@@ -1386,7 +1395,7 @@ struct RowOps {
             if (cur < S && now > cnt) {
                 inc &= ~(1ull << cur);
                 cur = S;
-                fl |= 1;  // OC_TASKF_COMPLETED
+                fl |= kTaskfCompleted;
             }
             int pick = S;
             float best = 0.0f, keep_lb = 0.0f;
@@ -1407,15 +1416,15 @@ struct RowOps {
                     keep_lb = lb;
                 }
             }
-            if ((flags & 2) && keep) {  // OC_TASK_COMMIT: cur is still a candidate
+            if ((flags & kTaskCommit) && keep) {  // cur is still a candidate
                 pick = cur;
                 best = keep_lb;
             }
             const int fresh = goal_objects(r, sm[pick < S ? pick : 0]);
             if (pick != cur && pick < S) cnt = fresh;
             cur = pick;
-            if (cur != entry) fl |= 2;  // OC_TASKF_SWITCHED
-            if ((flags & 4) && cur < S) taken |= 1ull << cur;  // OC_TASK_DISTINCT
+            if (cur != entry) fl |= kTaskfSwitched;
+            if ((flags & kTaskDistinct) && cur < S) taken |= 1ull << cur;
             for (int c = 0; c < EP; ++c) tm[c * P] = (uint8_t)(inc >> (8 * c));
             tm[EP * P] = (uint8_t)cur;
             tm[(EP + 1) * P] = (uint8_t)cnt;
@@ -1437,7 +1446,7 @@ struct RowOps {
     // host build is its own wave).
     OC_RH void team_env(Row r, const Sub* subs, int S, int flags, bool init, uint8_t* ts, float* bound, uint8_t* info,
                         int64_t P) {
-        const int EP = (S + 7) >> 3, kOut = 0xFF;
+        const int EP = (S + 7) >> 3;
         hold_cells(r);
         const BoundRow br = bound_row<true>(r);
         const uint32_t all = (1u << S) - 1u;
@@ -1449,9 +1458,9 @@ struct RowOps {
         if (init) {
             inc = all;
             cur0 = cur1 = S;
-            curJ = kOut;
+            curJ = kTeamOut;
             cnt0 = cnt1 = 0;
-            fl = 8;  // OC_TEAMF_REINIT
+            fl = kTeamfReinit;
         }
         const int e0 = cur0, e1 = cur1, eJ = curJ;
         // refresh: the counts of the current members (evaluated on every lane, used where a member is
@@ -1471,23 +1480,23 @@ struct RowOps {
             if (curJ < S) {
                 if (nJ > cnt0) {
                     inc &= ~(1u << curJ);
-                    fl |= 3;  // OC_TEAMF_COMPLETED0 | OC_TEAMF_COMPLETED1
+                    fl |= kTeamfCompleted0 | kTeamfCompleted1;
                 }
             } else {
                 if (cur0 < S && n0 > cnt0) {
                     inc &= ~(1u << cur0);
-                    fl |= 1;  // OC_TEAMF_COMPLETED0
+                    fl |= kTeamfCompleted0;
                 }
                 if (cur1 < S && n1 > cnt1) {
                     inc &= ~(1u << cur1);
-                    fl |= 2;  // OC_TEAMF_COMPLETED1
+                    fl |= kTeamfCompleted1;
                 }
             }
         }
         const bool dropped = (fl & 3) != 0;
         if (dropped) {
             cur0 = cur1 = S;
-            curJ = kOut;
+            curJ = kTeamOut;
         }
         // candidates: the two heaviest of each member, the heaviest joint one, and whether the
         // current members are candidates (> keeps the lowest index among equal weights)
@@ -1527,7 +1536,7 @@ struct RowOps {
             }
         }
         float b0 = 0.0f, b1 = 0.0f;
-        const bool keep = (flags & 2) && !dropped && (curJ < S ? kJ : cur0 < S && cur1 < S && k0 && k1);  // OC_TEAM_COMMIT
+        const bool keep = (flags & kTeamCommit) && !dropped && (curJ < S ? kJ : cur0 < S && cur1 < S && k0 && k1);
         if (keep) {
             b0 = curJ < S ? kJlb : k0lb;
             b1 = curJ < S ? kJlb : k1lb;
@@ -1543,22 +1552,22 @@ struct RowOps {
                 else p0 = s0, q0 = ls0, wS = y;
             }
             const bool full = p0 < S && p1 < S;
-            if ((flags & 4) && have && full) {  // OC_TEAM_SPLIT_FIRST
-                cur0 = p0, cur1 = p1, curJ = kOut;
+            if ((flags & kTeamSplitFirst) && have && full) {
+                cur0 = p0, cur1 = p1, curJ = kTeamOut;
                 b0 = q0, b1 = q1;
             } else if (iJ < S && (!have || wJ >= wS)) {
-                cur0 = cur1 = kOut, curJ = iJ;
+                cur0 = cur1 = kTeamOut, curJ = iJ;
                 b0 = b1 = lJ;
             } else if (have) {
-                cur0 = p0, cur1 = p1, curJ = kOut;
+                cur0 = p0, cur1 = p1, curJ = kTeamOut;
                 b0 = q0, b1 = q1;
             } else {
-                cur0 = cur1 = S, curJ = kOut;
-                fl |= 0x20;  // OC_TEAMF_IDLE
+                cur0 = cur1 = S, curJ = kTeamOut;
+                fl |= kTeamfIdle;
             }
         }
         if (cur0 != e0 || cur1 != e1 || curJ != eJ) {
-            fl |= 4;  // OC_TEAMF_SWITCHED
+            fl |= kTeamfSwitched;
             const int m0 = curJ < S ? curJ : cur0;  // a0's member
             int n0 = 0, n1 = 0;
 #pragma unroll 1
@@ -1571,7 +1580,7 @@ struct RowOps {
             cnt0 = curJ < S || cur0 < S ? n0 : 0;
             cnt1 = curJ >= S && cur1 < S ? n1 : 0;
         }
-        if (curJ < S) fl |= 0x10;  // OC_TEAMF_JOINT
+        if (curJ < S) fl |= kTeamfJoint;
         for (int c = 0; c < EP; ++c) ts[c * P] = (uint8_t)(inc >> (8 * c));
         ts[EP * P] = (uint8_t)cur0;
         ts[(EP + 1) * P] = (uint8_t)cur1;
@@ -1612,11 +1621,11 @@ struct RowOps {
             open = 1ull << S;
             for (int i = 0; i < S; ++i) open |= subs[i].kind != 0 ? 1ull << i : 0ull;
             uniform = true;
-            fl = 4;  // OC_BELF_REINIT
+            fl = kBelfReinit;
         } else if ((ev & subm & open) != 0ull) {
             open &= ~(ev & subm);
             uniform = true;
-            fl = 8;  // OC_BELF_RESET
+            fl = kBelfReset;
         }
         if (uniform) {
             live = open;
@@ -1639,7 +1648,7 @@ struct RowOps {
                 if (full_bound(br, r0, row_of(i), lb)) continue;
                 live &= ~(1ull << i);
                 belief[i * P] = 0.0;
-                fl |= 2;  // OC_BELF_PRUNED
+                fl |= kBelfPruned;
             }
             const bool any_sub = (live & subm) != 0ull;
             // 4. the raise test on a's Level-0 view (the same for every one-agent hypothesis)
@@ -1656,9 +1665,9 @@ struct RowOps {
                 for (int k = 0; k < 5; ++k) legal |= single_legal(v, a, k) ? 1u << k : 0u;
             raises = any_sub && (raises || !((legal >> t) & 1u));
             if (raises) {
-                fl |= 16;  // OC_BELF_RAISED
+                fl |= kBelfRaised;
             } else {
-                fl |= 1;  // OC_BELF_UPDATED
+                fl |= kBelfUpdated;
                 // 5. multiply: the successors once per env, the goal test and bound per hypothesis
                 Row succ[5];
                 if (any_sub)

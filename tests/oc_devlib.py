@@ -1,11 +1,13 @@
-"""Device twins of the host calls in tests/taskselect_ref.py and tests/belief_ref.py, shared by the
-GPU tests: oc_task_select and oc_belief_update on guard-filled device buffers with numpy in and
-out, and the comparison of a device call with the host call on the same bytes."""
+"""Device twins of the host calls in tests/taskselect_ref.py, tests/teamselect_ref.py and
+tests/belief_ref.py, shared by the GPU tests: oc_task_select, oc_team_select and oc_belief_update on
+guard-filled device buffers with numpy in and out, and the comparison of a device call with the
+host call on the same bytes."""
 import numpy as np
 import torch
 
 import belief_ref as br
 import taskselect_ref as tr
+import teamselect_ref as mr
 
 
 class TaskDev:
@@ -34,6 +36,27 @@ def task_assert_same(dev, host):
         assert (d is None) == (h is None)
         if d is not None:
             assert np.array_equal(d.view(np.uint8), h.view(np.uint8)), np.argwhere(d.view(np.uint8) != h.view(np.uint8))[:5]
+
+
+class TeamDev:
+    """oc_team_select on guard-filled device buffers, numpy in and out (as teamselect_ref.host_call)."""
+
+    def __init__(self, level, A, B):
+        from gym_cooking_amd.engine import OvercookedBatch
+        self.eb = OvercookedBatch(level, A, B, max_T=100, device="cuda:0")
+
+    def call(self, s, prev, rows, pair, flags, ts, want_bound=True, want_info=True, times=1):
+        P = self.eb.pitch
+        dts = torch.from_numpy(ts).cuda()
+        bound = torch.full((2, P), float("nan"), dtype=torch.float32, device="cuda:0") if want_bound else None
+        info = torch.full((P,), mr.GUARD_INFO, dtype=torch.uint8, device="cuda:0") if want_info else None
+        launch = self.eb.team_select_launcher(torch.from_numpy(s).cuda(), rows, pair, dts,
+                                              None if prev is None else torch.from_numpy(prev).cuda(), flags, bound, info)
+        for _ in range(times):
+            launch()
+        torch.cuda.synchronize()
+        return (dts.cpu().numpy(), None if bound is None else bound.cpu().numpy(),
+                None if info is None else info.cpu().numpy())
 
 
 class BeliefDev:

@@ -9,6 +9,8 @@ Per cell, each host twin against its independent restatement:
 
   * oc_cpu_task_select inside taskselect_ref.closed_loop, every agent scripted in descending
     order, checked at every step;
+  * oc_cpu_team_select inside teamselect_ref.closed_loop for the pair (0, A - 1), on the 27 cells
+    with two agents or more, checked at every step;
   * oc_cpu_belief_update inside belief_ref.closed_loop with all A agents watched;
   * oc_cpu_nav_policy on a random case against policy_ref.distribution in both count modes, on
     the joint table (25 candidates) and its one-agent reduction (5); with one agent the table has
@@ -34,6 +36,7 @@ import oc_testlib as tl
 import policy_ref
 import start_ref as sr
 import taskselect_ref as tr
+import teamselect_ref as mr
 import test_policy as tp
 import test_rollout_host as th
 from gym_cooking_amd import capi
@@ -43,6 +46,7 @@ from test_dispatch_grid import dense_level, grid_level
 SHAPES = ("narrow", "dense", "wide")
 SLOTS = (4, 8, 16)
 PLAN_CELLS = [(A, K, shape) for shape in SHAPES for K in SLOTS for A in (1, 2, 3, 4)]
+TEAM_CELLS = [cell for cell in PLAN_CELLS if cell[0] >= 2]  # a team needs two agents
 LEVELS = [(K, shape) for shape in SHAPES for K in SLOTS]
 # random_rollout_case's seed of each cell's random case: row (shape, K), column A = 1..4.  The cells
 # count up, except (2, 16, wide): seed 34 draws a table of one row, which has no joint rows
@@ -97,6 +101,18 @@ def task_loop(A: int, K: int, shape: str, check: bool, record_every: int = 0):
                           record_every=record_every, check=check)
 
 
+def team_pair(A: int):
+    """The team: the first and the last agent (with 3 or 4 agents the others act at random)."""
+    return (0, A - 1)
+
+
+def team_loop(A: int, K: int, shape: str, check: bool, record_every: int = 0):
+    """(Ref with its counters, records) of the team loop of team_pair(A)."""
+    ref, rec, _ = mr.closed_loop(plan_level(K, shape), A, team_pair(A), LOOP_B, LOOP_STEPS, mr.COMMIT, max_T=LOOP_MAX_T,
+                                 record_every=record_every, check=check)
+    return ref, rec
+
+
 def belief_loop(A: int, K: int, shape: str, check: bool, record_every: int = 0):
     """(Ref with its counters, records) of the loop with the belief update, every agent watched."""
     return br.closed_loop(plan_level(K, shape), A, scripted(A), LOOP_B, LOOP_STEPS, max_T=LOOP_MAX_T,
@@ -110,6 +126,11 @@ def task_counts(A: int, K: int, shape: str) -> dict:
 
 
 @functools.lru_cache(maxsize=None)
+def team_counts(A: int, K: int, shape: str) -> dict:
+    return dict(team_loop(A, K, shape, True)[0].n)
+
+
+@functools.lru_cache(maxsize=None)
 def belief_counts(A: int, K: int, shape: str) -> dict:
     return dict(belief_loop(A, K, shape, True)[0].n)
 
@@ -118,6 +139,13 @@ def belief_counts(A: int, K: int, shape: str) -> dict:
 def test_task_select_matches_restatement(A, K, shape):
     n = task_counts(A, K, shape)
     assert n["reinit"] >= 2 * LOOP_B  # the INIT call, and every env timing out at step 12 of the 16
+
+
+@pytest.mark.parametrize("A,K,shape", TEAM_CELLS)
+def test_team_select_matches_restatement(A, K, shape):
+    n = team_counts(A, K, shape)
+    assert n["reinit"] >= 2 * LOOP_B  # the INIT call, and every env timing out at step 12 of the 16
+    assert n["split"] >= 1 and n["completed"] >= 1, n
 
 
 @pytest.mark.parametrize("A,K,shape", PLAN_CELLS)
@@ -132,6 +160,15 @@ def test_loops_of_a_level_reach_completion_and_reset(K, shape):
     belief is reset by a completion event (single cells with 3 or 4 agents may see neither in 16 steps)."""
     assert sum(task_counts(A, K, shape)["completed"] for A in (1, 2, 3, 4)) >= 1
     assert sum(belief_counts(A, K, shape)["reset"] for A in (1, 2, 3, 4)) >= 1
+
+
+@pytest.mark.parametrize("K,shape", [level for level in LEVELS if level != (16, "wide")])
+def test_team_loops_of_a_level_reach_a_joint_allocation(K, shape):
+    """Over the three A of a level some env is played jointly (in 6 of the 27 single cells the pair
+    stays split for all 16 steps).  The wide 16-slot level is left out: its 768 env-steps are split
+    ones for every pair of every A, with COMMIT and with no flag, at this LOOP_B and LOOP_STEPS; the
+    idle branch does not occur in any cell's loop.  tests/test_teamselect.py reaches both."""
+    assert sum(team_counts(A, K, shape)["joint"] for A in (2, 3, 4)) >= 1
 
 
 def level0(subs):

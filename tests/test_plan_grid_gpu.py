@@ -9,8 +9,9 @@ cell at B = 203 (a partial word, lane group, wave and block everywhere):
     cells one more rollout has one row more than 64 per compute unit, the first size that leaves
     oc_rollout_group_kernel for the row-per-lane oc_rollout_kernel with its tables in LDS;
   * partner: oc_nav_policy (the four modes; 25 and 5 candidate planes), oc_task_select and
-    oc_belief_update (the recorded calls of the host loops, all A agents scripted and watched)
-    against the host twins on the same bytes;
+    oc_belief_update (the recorded calls of the host loops, all A agents scripted and watched) and,
+    with two agents or more, oc_team_select (the recorded calls of the team loop of agents 0 and
+    A - 1) against the host twins on the same bytes;
   * starts: oc_reset_random against oc_cpu_reset_random, the whole batch and masked by a state with
     DONE envs, at B = 7 and 203, guard bytes included."""
 import numpy as np
@@ -95,6 +96,13 @@ def test_partner_kernels_match_host(A, K, shape):
         dl.task_assert_same(dev.call(st, prev, rows, agents, fl, ts), (ts_after, bound, info))
         restarted |= not (fl & tr.INIT) and bool((info[:, :LB] & tr.REINIT).any())
     assert restarted  # some call started envs over from state_prev's DONE flags
+
+    if A >= 2:
+        _, rec = pg.team_loop(A, K, shape, False, pg.RECORD_EVERY)
+        assert len(rec) == pg.LOOP_STEPS
+        dev = dl.TeamDev(lv, A, LB)
+        for st, prev, fl, ts, ts_after, bound, info in rec:
+            dl.task_assert_same(dev.call(st, prev, rows, pg.team_pair(A), fl, ts), (ts_after, bound, info))
 
     _, rec = pg.belief_loop(A, K, shape, False, pg.RECORD_EVERY)
     assert len(rec) == pg.LOOP_STEPS + 1

@@ -19,30 +19,10 @@ from gym_cooking_amd.engine import CpuStepper
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+from oc_devlib import TeamDev as Dev  # noqa: E402
 from oc_devlib import task_assert_same as assert_same  # noqa: E402
 
 C = mr.COMMIT
-
-
-class Dev:
-    """oc_team_select on guard-filled device buffers, numpy in and out (as teamselect_ref.host_call)."""
-
-    def __init__(self, level, A, B):
-        from gym_cooking_amd.engine import OvercookedBatch
-        self.eb = OvercookedBatch(level, A, B, max_T=100, device="cuda:0")
-
-    def call(self, s, prev, rows, pair, flags, ts, want_bound=True, want_info=True, times=1):
-        P = self.eb.pitch
-        dts = torch.from_numpy(ts).cuda()
-        bound = torch.full((2, P), float("nan"), dtype=torch.float32, device="cuda:0") if want_bound else None
-        info = torch.full((P,), mr.GUARD_INFO, dtype=torch.uint8, device="cuda:0") if want_info else None
-        launch = self.eb.team_select_launcher(torch.from_numpy(s).cuda(), rows, pair, dts,
-                                              None if prev is None else torch.from_numpy(prev).cuda(), flags, bound, info)
-        for _ in range(times):
-            launch()
-        torch.cuda.synchronize()
-        return (dts.cpu().numpy(), None if bound is None else bound.cpu().numpy(),
-                None if info is None else info.cpu().numpy())
 
 
 @functools.lru_cache(maxsize=None)
