@@ -569,6 +569,11 @@ static_assert(ocro::kTeamCommit == OC_TEAM_COMMIT && ocro::kTeamSplitFirst == OC
 static_assert(ocro::kBelfUpdated == OC_BELF_UPDATED && ocro::kBelfPruned == OC_BELF_PRUNED &&
               ocro::kBelfReinit == OC_BELF_REINIT && ocro::kBelfReset == OC_BELF_RESET &&
               ocro::kBelfRaised == OC_BELF_RAISED, "oc_rollout.h: belief_env's flags");
+static_assert(ocro::kTbelfUpdated == OC_TBELF_UPDATED && ocro::kTbelfPruned == OC_TBELF_PRUNED &&
+              ocro::kTbelfReinit == OC_TBELF_REINIT && ocro::kTbelfReset == OC_TBELF_RESET &&
+              ocro::kTbelfRaised == OC_TBELF_RAISED && ocro::kTbelfEmpty == OC_TBELF_EMPTY &&
+              ocro::kTbelfJoint == OC_TBELF_JOINT && ocro::kTeamMaxSubtasks == OC_TEAM_MAX_SUBTASKS,
+              "oc_rollout.h: team_belief_env's flags");
 
 // Stage the level's table blob and the subtask configurations in LDS.
 template <int NT = kBlock>
@@ -1672,6 +1677,248 @@ __global__ __launch_bounds__(kBlock) void oc_belief_kernel(RollArgs R, BeliefArg
             }
             if (map != nullptr) map[m * P + e] = (uint8_t)best;
             if (info != nullptr) info[m * P + e] = (uint8_t)fl;
+        }
+        wave_lds_sync();  // the group's slots are free for its next env
+    }
+}
+
+// The posterior over a pair's allocation (oc_team_belief_update), oc_belief_kernel's shape run over
+// three families of members: a0's one-agent rows, a1's, and the pair's two-agent rows
+// (oc_team_select's staging of the 3 x S configurations).  A group of 8 lanes per env; per family
+// every lane builds the family's Level-0 view, lane k < 5 tests candidate k's legality and keeps
+// its successor row (for the pair: self's action k beside the other member's taken action), lane 5
+// keeps state_prev's own row with the full-state view for the doable test, and the S rows are
+// walked with a wave-uniform index (a row no group of the wave has live is skipped).  The family
+// index is a rolled, wave-uniform loop: one copy of the walk per build.  The group's 3 S + 2
+// likelihoods sit in LDS in `lik`'s plane order.
+// The posterior pass runs in the same kernel, because `lik` may be NULL and the call allocates
+// nothing: a second kernel would have no workspace to read the likelihoods and pruned sets from.
+// It keeps no hypothesis-indexed registers: row i is a group-uniform loop and lane l takes the
+// columns j = l, l + 8, ..; a first sweep reads the beliefs and sums belief * factor, a second one
+// reads them again (the same lane, the same planes), scales and stores, and keeps the first maximum
+// in reference order by the hypothesis' key.  Each plane access of a wave covers 8 consecutive envs.
+struct TBeliefArgs {
+    double beta, nap;
+    int32_t S, flags;
+    uint8_t a0, a1, self, pad;
+};
+constexpr int kTBeliefLik = 3 * (OC_TEAM_MAX_SUBTASKS + 1);  // a group's likelihood slots (>= 3 S + 2)
+// the kernel's static LDS: the subtask rows and the groups' likelihoods (18 KB; allow_dyn_lds counts it)
+constexpr int kTBeliefStaticLds = (int)(OC_MAX_SUBTASKS * sizeof(ocro::Sub)) + (kBlock / 8) * kTBeliefLik * (int)sizeof(double);
+template <int A, int K, bool W, bool GD>
+__global__ __launch_bounds__(kBlock) void oc_team_belief_kernel(RollArgs R, TBeliefArgs Q, const uint8_t* __restrict__ sprev,
+                                                                const uint8_t* __restrict__ taken,
+                                                                const uint8_t* __restrict__ events,
+                                                                const uint8_t* __restrict__ blob_g, double* __restrict__ bel,
+                                                                uint8_t* __restrict__ ts, double* __restrict__ lik,
+                                                                uint8_t* __restrict__ map, uint8_t* __restrict__ info) {
+    constexpr int G = 8;
+    extern __shared__ __attribute__((aligned(16))) uint32_t blob_w[];
+    __shared__ ocro::Sub subs[OC_MAX_SUBTASKS];
+    __shared__ double ll[kBlock / G][kTBeliefLik];  // a group's L0 at [0, N), L1 at [N, 2N), LJ at [2N, 2N + S)
+    stage_roll_tables(R, blob_g, blob_w, subs);
+    const uint8_t* blob = (const uint8_t*)blob_w;
+    const int64_t P = R.pitch;
+    using Row = ocro::RowT<K, W>;
+    const int lane = (int)(threadIdx.x & (G - 1));
+    const int S = Q.S, N = S + 1, HP = (S + 8) >> 3, EP = (S + 7) >> 3;
+    const int a0 = Q.a0, a1 = Q.a1;
+    const bool self_first = Q.self == Q.a0;
+    const uint32_t subm = (1u << S) - 1u, none = 1u << S;
+    uint32_t real = 0u;  // the subtasks a fresh distribution holds
+    for (int i = 0; i < S; ++i) real |= subs[i].kind != 0 ? 1u << i : 0u;
+    double* mine = ll[threadIdx.x / G];
+    const int64_t ngroups = (int64_t)gridDim.x * (kBlock / G);
+    for (int64_t e = (int64_t)blockIdx.x * (kBlock / G) + threadIdx.x / G; e < R.B; e += ngroups) {
+        // group-uniform from here on, except where `lane` is named
+        const bool init = starts_over<A, K, W>((Q.flags & OC_TBELIEF_INIT) != 0, sprev, P, e);
+        uint32_t open = 0u, l0 = 0u, l1 = 0u, lJ = 0u, ev = 0u;
+        if (!init) {
+            for (int c = 0; c < EP; ++c) {
+                open |= (uint32_t)ts[c * P + e] << (8 * c);
+                lJ |= (uint32_t)ts[(EP + 2 * HP + c) * P + e] << (8 * c);
+                if (events != nullptr) ev |= (uint32_t)events[c * P + e] << (8 * c);
+            }
+            for (int c = 0; c < HP; ++c) {
+                l0 |= (uint32_t)ts[(EP + c) * P + e] << (8 * c);
+                l1 |= (uint32_t)ts[(EP + HP + c) * P + e] << (8 * c);
+            }
+        }
+        open &= real;
+        lJ &= real;
+        l0 &= real | none;
+        l1 &= real | none;
+        int fl = 0;
+        bool uniform = false;
+        if (init) {
+            open = real;
+            uniform = true;
+            fl = OC_TBELF_REINIT;
+        } else if ((ev & open) != 0u) {
+            open &= ~ev;
+            uniform = true;
+            fl = OC_TBELF_RESET;
+        }
+        uint32_t e0 = subm | none, e1 = subm | none, eJ = subm;  // the planes this call writes: the sets at entry
+        bool mult = false;  // step 6 runs
+        using Ops = ocro::RowOps<A, K, W, true, GD>;
+        if (uniform) {
+            l0 = l1 = open | none;
+            lJ = open;
+        } else {
+            e0 = l0, e1 = l1, eJ = lJ;
+            for (int i = lane; i < 3 * N; i += G) mine[i] = 0.0;
+            wave_lds_sync();
+            const Row r0 = load_row<A, K, W>(sprev, P, e);
+            int t0 = taken[a0 * P + e], t1 = taken[a1 * P + e];
+            t0 = t0 > ocro::kNoop ? ocro::kNoop : t0;
+            t1 = t1 > ocro::kNoop ? ocro::kNoop : t1;
+            Ops ops = plan_ops<A, K, W, true, GD>(R, blob, blob_g, false);  // the bound walk, as the likelihood kernels
+            const int n_self = __builtin_popcount(ops.none_movable(r0, Q.self));  // None: the self agent's movable actions
+            double p0, p1;
+            bool noop_mode;
+            ops.none_probs(n_self, Q.beta, Q.nap, p0, p1, noop_mode);
+            uint32_t rmask = 0u;  // bit f: family f raises
+#pragma unroll 1
+            for (int f = 0; f < 3; ++f) {  // a0 alone, a1 alone, the pair: wave-uniform
+                uint32_t lf = f == 0 ? l0 : f == 1 ? l1 : lJ;
+                if (!ocro::wave_any((lf & subm) != 0u)) continue;
+                const ocro::Sub cf = Ops::team_family(f, a0, a1);
+                const int tk = f == 0 ? t0 : f == 1 ? t1 : (self_first ? t0 : t1);  // the taken candidate
+                ops.ac = ops.kNoAc;
+                Row v = r0;
+                const bool raised0 = ops.level0(v, cf);
+                int c0, c1;
+                Ops::team_candidate(f, self_first, lane < 5 ? lane : ocro::kNoop, t0, t1, c0, c1);
+                const bool lg = lane < 5 && !raised0 && ops.action_legal(v, cf, c0, c1);
+                // the row this lane bounds: candidate k's successor on lane k, state_prev itself on lane 5
+                Row rb = v;
+                double cost = 1.0;
+                int coloc = 0;
+                if (lg) coloc = ops.team_successor(rb, cf, c0, c1, cost) ? 0 : 1;
+#pragma unroll
+                for (int off = 1; off < G; off <<= 1) coloc |= __shfl_xor(coloc, off, G);
+                const bool rc = raised0 || !__shfl((int)lg, tk, G) || coloc != 0;  // the family raises
+                if (lane >= 5) {
+                    rb = r0;
+                    ops.ac = ops.kNoAc;
+                }
+                const bool worker = lane == 5 || (lg && !rc);
+#pragma unroll 1
+                for (int i = 0; i < S; ++i) {
+                    const bool li = ((lf >> i) & 1u) != 0u;
+                    if (!ocro::wave_any(li)) continue;  // wave-uniform
+                    const ocro::Sub& s = subs[f * S + i];
+                    // lane 5: q_successor's bound-only form on state_prev itself; its `dist` is the
+                    // doable test's distance (full_bound's, with the same full-state configuration)
+                    const int count = lane < 5 ? ops.goal_objects(v, s) : Ops::kBoundOnly;
+                    double q = 0.0;
+                    float dist = 0.0f;
+                    if (li && worker) q = ops.q_successor(rb, s, count, cost, dist);
+                    if (!li) continue;
+                    if (__shfl((int)(dist < (float)R.L.perimeter), 5, G) == 0) {  // not doable
+                        lf &= ~(1u << i);
+                        continue;
+                    }
+                    if (rc) continue;
+                    double mq = lg ? q : 1.0e300;
+#pragma unroll
+                    for (int off = 1; off < G; off <<= 1) {
+                        const double o = __shfl_xor(mq, off, G);
+                        mq = o < mq ? o : mq;
+                    }
+                    const double w = lg ? exp(Q.beta * (mq - q)) : 0.0;
+                    double sum = 0.0;  // ascending k: the sequential sum
+                    for (int c = 0; c < 5; ++c) sum += __shfl(w, c, G);
+                    const double l = __shfl(w / sum, tk, G);
+                    if (lane == 0) mine[f * N + i] = l;
+                }
+                if (f == 0) l0 = lf;
+                else if (f == 1) l1 = lf;
+                else lJ = lf;
+                rmask |= rc ? 1u << f : 0u;
+            }
+            const int n_live = Ops::team_live_count(l0, l1, lJ);
+            if (n_live < Ops::team_live_count(e0, e1, eJ)) fl |= OC_TBELF_PRUNED;
+            if (n_live == 0) {
+                fl |= OC_TBELF_EMPTY;
+            } else {
+                const bool raised = ((rmask & 1u) && Ops::team_needs(l0, l1, subm)) ||
+                                    ((rmask & 2u) && Ops::team_needs(l1, l0, subm)) || ((rmask & 4u) && lJ != 0u);
+                mult = !raised;
+                fl |= raised ? OC_TBELF_RAISED : OC_TBELF_UPDATED;
+                if (lane == 0) {  // (a raising family's members kept their +0.0)
+                    mine[S] = t0 == ocro::kNoop ? p0 : p1;
+                    mine[N + S] = t1 == ocro::kNoop ? p0 : p1;
+                }
+            }
+        }
+        wave_lds_sync();
+        // steps 6 to 8: row i group-uniform, this lane's columns j
+        const int n_live = Ops::team_live_count(l0, l1, lJ);
+        const double u = 1.0 / (double)n_live;
+        auto live = [&](int i, int j) {
+            return i == j ? i < S && ((lJ >> i) & 1u) != 0u : ((l0 >> i) & 1u) != 0u && ((l1 >> j) & 1u) != 0u;
+        };
+        auto value = [&](int i, int j) {  // the live hypothesis' belief before step 7
+            if (uniform) return u;
+            double x = bel[(int64_t)(i * N + j) * P + e];
+            if (mult) x = x * (i == j ? 2.0 * mine[2 * N + i] : mine[i] + mine[N + j]);
+            return x;
+        };
+        double total = 0.0;
+        for (int i = 0; i < N; ++i)
+            for (int j = lane; j < N; j += G)
+                if (live(i, j)) total += value(i, j);
+#pragma unroll
+        for (int off = 1; off < G; off <<= 1) total += __shfl_xor(total, off, G);
+        const double r = total == 0.0 ? u : 1.0 / total;
+        double bv = -1.0;
+        int key = -1;
+        for (int i = 0; i < N; ++i)
+            for (int j = lane; j < N; j += G) {
+                const bool was = i == j ? i < S && ((eJ >> i) & 1u) != 0u : ((e0 >> i) & 1u) != 0u && ((e1 >> j) & 1u) != 0u;
+                if (!was) continue;
+                double x = 0.0;
+                if (live(i, j)) {
+                    x = value(i, j);
+                    x = total == 0.0 ? r : x * r;
+                    const int k = i == j ? i : S + i * N + j;
+                    if (x > bv || (x == bv && k < key)) {
+                        bv = x;
+                        key = k;
+                    }
+                }
+                bel[(int64_t)(i * N + j) * P + e] = x;
+            }
+#pragma unroll
+        for (int off = 1; off < G; off <<= 1) {
+            const double ov = __shfl_xor(bv, off, G);
+            const int ok = __shfl_xor(key, off, G);
+            const bool take = ov > bv || (ov == bv && ok < key);
+            bv = take ? ov : bv;
+            key = take ? ok : key;
+        }
+        if (mult && lik != nullptr)
+            for (int i = lane; i < 3 * S + 2; i += G) lik[(int64_t)i * P + e] = mine[i];
+        if (lane == 0) {
+            int m0, m1, mJ;
+            Ops::team_map_bytes(key, S, m0, m1, mJ);
+            if (mJ < S) fl |= OC_TBELF_JOINT;
+            for (int c = 0; c < EP; ++c) {
+                ts[c * P + e] = (uint8_t)(open >> (8 * c));
+                ts[(EP + 2 * HP + c) * P + e] = (uint8_t)(lJ >> (8 * c));
+            }
+            for (int c = 0; c < HP; ++c) {
+                ts[(EP + c) * P + e] = (uint8_t)(l0 >> (8 * c));
+                ts[(EP + HP + c) * P + e] = (uint8_t)(l1 >> (8 * c));
+            }
+            if (map != nullptr) {
+                map[e] = (uint8_t)m0;
+                map[P + e] = (uint8_t)m1;
+                map[2 * P + e] = (uint8_t)mJ;
+            }
+            if (info != nullptr) info[e] = (uint8_t)fl;
         }
         wave_lds_sync();  // the group's slots are free for its next env
     }
@@ -3586,6 +3833,117 @@ int oc_cpu_belief_update(const oc_handle* h, const void* state_prev, const uint8
             }
         }
         return OC_OK;
+    });
+}
+
+// oc_team_belief_update / oc_cpu_team_belief_update: the arguments both check, and the call's
+// RollArgs (oc_team_select's staging: a0's S one-agent Level-0 configurations at rows 0 .., a1's at
+// S .., the two-agent ones at 2S ..) and TBeliefArgs
+static int team_belief_args(const oc_handle* h, const void* state_prev, const uint8_t* taken, const oc_subtask* subtasks,
+                            int32_t num_subtasks, const uint8_t* agents, int32_t self_agent, double beta, double nap,
+                            int32_t flags, const double* belief, const uint8_t* tbstate, const double* lik, int64_t B,
+                            bool host, RollArgs& R, TBeliefArgs& Q) {
+    if (subtasks == nullptr || agents == nullptr || belief == nullptr || tbstate == nullptr)
+        return fail(OC_EINVAL, "team_belief_update: subtasks, agents, belief and tbstate are required");
+    if (B < 0) return fail(OC_EINVAL, "team_belief_update: B %lld", (long long)B);
+    const int32_t S = num_subtasks;
+    if (h->A < 2) return fail(OC_EINVAL, "team_belief_update: a team needs 2 agents, the handle has %d", h->A);
+    if (S < 1 || S > OC_TEAM_MAX_SUBTASKS)
+        return fail(OC_EINVAL, "team_belief_update: num_subtasks %d (1..%d)", S, OC_TEAM_MAX_SUBTASKS);
+    if (flags < 0 || flags > OC_TBELIEF_INIT) return fail(OC_EINVAL, "team_belief_update: flags %d", flags);
+    if (!(flags & OC_TBELIEF_INIT) && (state_prev == nullptr || taken == nullptr))
+        return fail(OC_EINVAL, "team_belief_update: state_prev and taken are required without OC_TBELIEF_INIT");
+    if (!(beta == beta) || !(nap >= 0.0 && nap <= 1.0))
+        return fail(OC_EINVAL, "team_belief_update: beta %g, none_action_prob %g", beta, nap);
+    if (agents[0] >= h->A || agents[1] >= h->A)
+        return fail(OC_EINVAL, "team_belief_update: agent %d", agents[0] >= h->A ? agents[0] : agents[1]);
+    if (agents[0] >= agents[1])
+        return fail(OC_EINVAL, "team_belief_update: agents %d, %d not ascending", agents[0], agents[1]);
+    if (self_agent != agents[0] && self_agent != agents[1])
+        return fail(OC_EINVAL, "team_belief_update: self_agent %d is not in the pair (%d, %d)", self_agent, agents[0],
+                    agents[1]);
+    if (((uintptr_t)belief & 7u) || ((uintptr_t)lik & 7u) || ((uintptr_t)state_prev & 1u))
+        return fail(OC_EINVAL, "team_belief_update: misaligned buffer");
+    oc_subtask rows[OC_MAX_SUBTASKS];
+    for (int c = 0; c < 3; ++c)
+        for (int i = 0; i < S; ++i) {
+            const bool two = c == 2 && subtasks[i].kind != OC_SUB_NONE;  // a None row is a one-agent row and never a hypothesis
+            rows[c * S + i] = two ? level0_row(subtasks[i], agents[0], agents[1]) : level0_row(subtasks[i], agents[c == 1 ? 1 : 0]);
+        }
+    if (const int rc = roll_args(h, rows, 3 * S, B, R, false, host)) return rc;
+    Q.beta = beta;
+    Q.nap = nap;
+    Q.S = S;
+    Q.flags = flags;
+    Q.a0 = agents[0];
+    Q.a1 = agents[1];
+    Q.self = (uint8_t)self_agent;
+    Q.pad = 0;
+    return OC_OK;
+}
+
+int oc_team_belief_update(const oc_handle* h, const void* state_prev, const uint8_t* taken, const uint8_t* events,
+                          const oc_subtask* subtasks, int32_t num_subtasks, const uint8_t* agents, int32_t self_agent,
+                          double beta, double none_action_prob, int32_t flags, double* belief, uint8_t* tbstate,
+                          double* lik, uint8_t* map, uint8_t* info, int64_t B, void* stream) {
+    if (h == nullptr) return fail(OC_EINVAL, "bad argument");
+    ErrScope es_(h);
+    OC_NEED_DEVICE(h);
+    RollArgs R;
+    TBeliefArgs Q;
+    if (const int rc = team_belief_args(h, state_prev, taken, subtasks, num_subtasks, agents, self_agent, beta,
+                                        none_action_prob, flags, belief, tbstate, lik, B, false, R, Q))
+        return rc;
+    if (B == 0) return OC_OK;
+    const dim3 grid(env_grid(h, B, kBlock / 8, 8));  // oc_belief_update's grid for 8-lane groups
+    hipStream_t st = (hipStream_t)stream;
+    return dispatch_plan(h, [&](auto a, auto k, auto w, auto gd) {
+        if constexpr (decltype(a)::value < 2) {
+            return fail(OC_EINVAL, "team_belief_update: a team needs 2 agents");
+        } else {
+            return launch_staged(oc_team_belief_kernel<a(), k(), w(), gd()>, grid, dim3(kBlock), R, st,
+                                 "oc_team_belief_update launch", kTBeliefStaticLds, Q, (const uint8_t*)state_prev, taken,
+                                 events, (const uint8_t*)h->roll_blob, belief, tbstate, lik, map, info);
+        }
+    });
+}
+
+int oc_cpu_team_belief_update(const oc_handle* h, const void* state_prev, const uint8_t* taken, const uint8_t* events,
+                              const oc_subtask* subtasks, int32_t num_subtasks, const uint8_t* agents,
+                              int32_t self_agent, double beta, double none_action_prob, int32_t flags, double* belief,
+                              uint8_t* tbstate, double* lik, uint8_t* map, uint8_t* info, int64_t B, int32_t nthreads) {
+    if (h == nullptr || nthreads < 0) return fail(OC_EINVAL, "bad argument");
+    ErrScope es_(h);
+    RollArgs R;
+    TBeliefArgs Q;
+    if (const int rc = team_belief_args(h, state_prev, taken, subtasks, num_subtasks, agents, self_agent, beta,
+                                        none_action_prob, flags, belief, tbstate, lik, B, true, R, Q))
+        return rc;
+    if (B == 0) return OC_OK;
+    const uint8_t* blob = h->roll_blob_host.data();
+    const uint8_t* sprev = (const uint8_t*)state_prev;
+    // >= 1,024 rows (3 x S members each) per thread
+    return host_ranges(h, nthreads, B, 1024, [&](auto a, auto k, auto w, int64_t e0, int64_t e1) {
+        if constexpr (decltype(a)::value < 2) {
+            return fail(OC_EINVAL, "team_belief_update: a team needs 2 agents");
+        } else {
+            using Row = ocro::RowT<k(), w()>;
+            const int64_t P = R.pitch;
+            const int S = Q.S, EP = (S + 7) >> 3;
+            for (int64_t e = e0; e < e1; ++e) {
+                const bool init = starts_over<a(), k(), w()>((Q.flags & OC_TBELIEF_INIT) != 0, sprev, P, e);
+                uint32_t ev = 0u;
+                if (!init && events != nullptr)
+                    for (int c = 0; c < EP; ++c) ev |= (uint32_t)events[c * P + e] << (8 * c);
+                const Row r0 = init ? Row{} : load_row<a(), k(), w()>(sprev, P, e);
+                ocro::RowOps<a(), k(), w(), true, true> ops(R.L, blob);
+                ops.team_belief_env(r0, R.subs, S, Q.a0, Q.a1, Q.self, init ? ocro::kNoop : (int)taken[Q.a0 * P + e],
+                                    init ? ocro::kNoop : (int)taken[Q.a1 * P + e], ev, init, Q.beta, Q.nap, belief + e,
+                                    tbstate + e, lik != nullptr ? lik + e : nullptr, map != nullptr ? map + e : nullptr,
+                                    info != nullptr ? info + e : nullptr, P);
+            }
+            return OC_OK;
+        }
     });
 }
 

@@ -64,8 +64,8 @@ constexpr uint8_t kNone = 0xFF;
 constexpr uint16_t kNoNode = 0xFFFF;
 constexpr int kFloor = 0, kCounter = 1, kCutboard = 2, kDelivery = 3;  // OC_TILE_*
 constexpr int kNoop = 4;
-// The partner rules' flag values: the OC_TASK_*, OC_TASKF_*, OC_TEAM_*, OC_TEAMF_* and OC_BELF_*
-// macros of include/oc_engine.h under this header's own names (it stands alone; oc_engine.hip,
+// The partner rules' flag values: the OC_TASK_*, OC_TASKF_*, OC_TEAM_*, OC_TEAMF_*, OC_BELF_* and
+// OC_TBELF_* macros of include/oc_engine.h under this header's own names (it stands alone; oc_engine.hip,
 // which includes both, asserts that each pair agrees).
 constexpr int kTaskCommit = 2, kTaskDistinct = 4;
 constexpr int kTaskfCompleted = 0x01, kTaskfSwitched = 0x02, kTaskfReinit = 0x04;
@@ -73,6 +73,9 @@ constexpr int kTeamCommit = 2, kTeamSplitFirst = 4, kTeamOut = 0xFF;
 constexpr int kTeamfCompleted0 = 0x01, kTeamfCompleted1 = 0x02, kTeamfSwitched = 0x04, kTeamfReinit = 0x08,
               kTeamfJoint = 0x10, kTeamfIdle = 0x20;
 constexpr int kBelfUpdated = 0x01, kBelfPruned = 0x02, kBelfReinit = 0x04, kBelfReset = 0x08, kBelfRaised = 0x10;
+constexpr int kTeamMaxSubtasks = 21;
+constexpr int kTbelfUpdated = 0x01, kTbelfPruned = 0x02, kTbelfReinit = 0x04, kTbelfReset = 0x08, kTbelfRaised = 0x10,
+              kTbelfEmpty = 0x20, kTbelfJoint = 0x40;
 constexpr int kDX[5] = {0, 0, -1, 1, 0}, kDY[5] = {1, -1, 0, 0, 0};  // World.NAV_ACTIONS + (0, 0)
 
 // Static level tables, one byte blob (offsets in RollLevel, set by build_roll_level):
@@ -1725,6 +1728,261 @@ struct RowOps {
             bs[(HP + c) * P] = (uint8_t)(live >> (8 * c));
         }
         if (map != nullptr) *map = (uint8_t)best;
+        if (info != nullptr) *info = (uint8_t)fl;
+    }
+
+    // ---- oc_team_belief_update: the posterior over a pair's allocation -------------------------
+    // The number of live hypotheses of the factored live sets: the joints, and the splits (i, j),
+    // i != j, with i in l0 and j in l1 (bit S = None in both).
+    OC_RH static int team_live_count(uint32_t l0, uint32_t l1, uint32_t lJ) {
+        return __builtin_popcount(lJ) + __builtin_popcount(l0) * __builtin_popcount(l1) - __builtin_popcount(l0 & l1);
+    }
+    // Some live split has a subtask (not None) as the member of the agent whose set is `mine`.
+    // In a state the call itself wrote, bit S (None) is in both sets (nothing prunes it), so this is
+    // (mine & subm) != 0; the loop over the members matters only for a tbstate the caller altered.
+    OC_RH static bool team_needs(uint32_t mine, uint32_t others, uint32_t subm) {
+        bool need = false;
+        for (uint32_t v = mine & subm; v; v &= v - 1u) need |= (others & ~(v & (0u - v))) != 0u;
+        return need;
+    }
+    // The map of step 8 as oc_team_select's three cur bytes, from the hypothesis' key in reference
+    // order (joint t: t; split (i, j): S + i * (S + 1) + j); key < 0: nothing is live, the idle split.
+    OC_RH static void team_map_bytes(int key, int S, int& c0, int& c1, int& cJ) {
+        c0 = c1 = S;
+        cJ = kTeamOut;
+        if (key >= 0 && key < S) {
+            c0 = c1 = kTeamOut;
+            cJ = key;
+        } else if (key >= S) {
+            c0 = (key - S) / (S + 1);
+            c1 = (key - S) % (S + 1);
+        }
+    }
+    // One family's view of state_prev for the likelihoods: the Level-0 configuration of the
+    // family's agents (cf), and the joint action of candidate k: the acting member's action k beside
+    // the other member's taken action (pair family; self acts), or action k alone.
+    OC_RH static Sub team_family(int f, int a0, int a1) {
+        Sub cf{};
+        cf.kind = 1;
+        cf.n = f == 2 ? 2 : 1;
+        cf.agent[0] = (uint8_t)(f == 1 ? a1 : a0);
+        cf.agent[1] = (uint8_t)(f == 2 ? a1 : cf.agent[0]);
+        cf.level = 0;
+        return cf;
+    }
+    OC_RH static void team_candidate(int f, bool self_first, int k, int t0, int t1, int& c0, int& c1) {
+        c0 = k;
+        c1 = kNoop;
+        if (f == 2) {
+            c0 = self_first ? k : t0;
+            c1 = self_first ? t1 : k;
+        }
+    }
+    // Candidate (c0, c1)'s successor of the family's view v; false where T raises (the pair ends on
+    // one square).  cost: time_cost + action_cost per moving agent (q_value's).
+    OC_RH bool team_successor(Row& r, const Sub& cf, int c0, int c1, double& cost) const {
+        interact(r, cf.agent[0], c0);
+        cost = 1.0;
+        if (c0 != kNoop) cost += 0.1;
+        if (cf.n == 2) {
+            interact(r, cf.agent[1], c1);
+            if (c1 != kNoop) cost += 0.1;
+            if (agent_cell(r, cf.agent[0]) == agent_cell(r, cf.agent[1])) return false;
+        }
+        return true;
+    }
+
+    // One env of oc_team_belief_update (include/oc_engine.h, "The rule"), the whole row on one lane:
+    // the host call's row (the kernel spreads the same steps over a lane group).  subs: a0's S
+    // one-agent rows, a1's at S .., the two-agent rows at 2S .. (oc_team_select's staging).  r0 =
+    // state_prev's row (unread when init), t0 / t1 = the pair's executed actions, ev = the step's
+    // events (0 = none given).  belief / ts / lik / map / info point at column e, planes P apart.
+    //   add_subtasks' order, prune_subtask_allocs            bayesian_delegator.py:697-886, :200-256
+    //   bayes_update (sum over members of len * p)           bayesian_delegator.py:1026-1072
+    //   prob_nav_actions (self inside the pair: 5 candidates) bayesian_delegator.py:461-689
+    //   normalize, get_max                                   utils.py:186-215
+    OC_RH void team_belief_env(const Row& r0, const Sub* subs, int S, int a0, int a1, int self, int t0, int t1,
+                               uint32_t ev, bool init, double beta, double nap, double* belief, uint8_t* ts, double* lik,
+                               uint8_t* map, uint8_t* info, int64_t P) {
+        const int N = S + 1, EP = (S + 7) >> 3, HP = (S + 8) >> 3;
+        const uint32_t subm = (1u << S) - 1u, none = 1u << S;
+        uint32_t real = 0u;
+        for (int i = 0; i < S; ++i) real |= subs[i].kind != 0 ? 1u << i : 0u;
+        uint32_t open = 0u, l0 = 0u, l1 = 0u, lJ = 0u;
+        for (int c = 0; c < EP; ++c) {
+            open |= (uint32_t)ts[c * P] << (8 * c);
+            lJ |= (uint32_t)ts[(EP + 2 * HP + c) * P] << (8 * c);
+        }
+        for (int c = 0; c < HP; ++c) {
+            l0 |= (uint32_t)ts[(EP + c) * P] << (8 * c);
+            l1 |= (uint32_t)ts[(EP + HP + c) * P] << (8 * c);
+        }
+        open &= real;
+        lJ &= real;
+        l0 &= real | none;
+        l1 &= real | none;
+        int fl = 0;
+        bool uniform = false, normalise = true;
+        if (init) {
+            open = real;
+            uniform = true;
+            fl = kTbelfReinit;
+        } else if ((ev & open) != 0u) {
+            open &= ~ev;
+            uniform = true;
+            fl = kTbelfReset;
+        }
+        auto is_live = [&](int i, int j) OC_RL {
+            return i == j ? i < S && ((lJ >> i) & 1u) != 0u : ((l0 >> i) & 1u) != 0u && ((l1 >> j) & 1u) != 0u;
+        };
+        if (uniform) {
+            l0 = l1 = open | none;
+            lJ = open;
+            const double u = 1.0 / (double)team_live_count(l0, l1, lJ);
+            for (int i = 0; i < N; ++i)
+                for (int j = 0; j < N; ++j)
+                    if (i != S || j != S) belief[(i * N + j) * P] = is_live(i, j) ? u : 0.0;
+        } else {
+            t0 = t0 > kNoop ? kNoop : t0;
+            t1 = t1 > kNoop ? kNoop : t1;
+            const uint32_t e0 = l0, e1 = l1, eJ = lJ;  // the sets at entry
+            // 3. prune: oc_subtask_bounds' doable byte of each member on the full state
+            const BoundRow br = bound_row<true>(r0);
+            for (int f = 0; f < 3; ++f) {
+                uint32_t& lf = f == 0 ? l0 : f == 1 ? l1 : lJ;
+                for (int i = 0; i < S; ++i) {
+                    float lb;
+                    if (((lf >> i) & 1u) && !full_bound(br, r0, subs[f * S + i], lb)) lf &= ~(1u << i);
+                }
+            }
+            const int n_live = team_live_count(l0, l1, lJ);
+            if (n_live < team_live_count(e0, e1, eJ)) {
+                fl |= kTbelfPruned;
+                for (int i = 0; i < N; ++i)
+                    for (int j = 0; j < N; ++j) {
+                        const bool was = i == j ? i < S && ((eJ >> i) & 1u) : ((e0 >> i) & 1u) && ((e1 >> j) & 1u);
+                        if (was && !is_live(i, j)) belief[(i * N + j) * P] = 0.0;
+                    }
+            }
+            if (n_live == 0) {
+                fl |= kTbelfEmpty;
+                normalise = false;
+            } else {
+                // 5. the raise test and the likelihoods, family by family: a0 alone, a1 alone, the pair
+                const bool self_first = self == a0;
+                const int n_self = __builtin_popcount(none_movable(r0, self));
+                double p0, p1;
+                bool noop_mode;
+                none_probs(n_self, beta, nap, p0, p1, noop_mode);
+                double L[3 * (kTeamMaxSubtasks + 1)];
+                for (int i = 0; i < 3 * N; ++i) L[i] = 0.0;
+                L[S] = t0 == kNoop ? p0 : p1;
+                L[N + S] = t1 == kNoop ? p0 : p1;
+                const bool need[3] = {team_needs(l0, l1, subm), team_needs(l1, l0, subm), lJ != 0u};
+                bool raised = false;
+                for (int f = 0; f < 3; ++f) {
+                    const uint32_t lf = f == 0 ? l0 : f == 1 ? l1 : lJ;
+                    if ((lf & subm) == 0u) continue;
+                    const Sub cf = team_family(f, a0, a1);
+                    const int tk = f == 0 ? t0 : f == 1 ? t1 : (self_first ? t0 : t1);  // the taken candidate
+                    ac = kNoAc;
+                    Row v = r0;
+                    bool rf = level0(v, cf);
+                    uint32_t legal = 0u;
+                    Row succ[5];
+                    double cost[5];
+                    for (int k = 0; k < 5 && !rf; ++k) {
+                        int c0, c1;
+                        team_candidate(f, self_first, k, t0, t1, c0, c1);
+                        succ[k] = v;
+                        cost[k] = 0.0;
+                        if (!action_legal(v, cf, c0, c1)) continue;
+                        legal |= 1u << k;
+                        rf |= !team_successor(succ[k], cf, c0, c1, cost[k]);
+                    }
+                    rf = rf || !((legal >> tk) & 1u);
+                    if (rf) {
+                        raised |= need[f];
+                        continue;
+                    }
+                    for (int i = 0; i < S; ++i) {
+                        if (!((lf >> i) & 1u)) continue;
+                        const Sub& s = subs[f * S + i];
+                        const int count = goal_objects(v, s);
+                        double q[5], m = 1.0e300;
+                        for (int k = 0; k < 5; ++k) {
+                            if (!((legal >> k) & 1u)) continue;
+                            float dist;
+                            q[k] = q_successor(succ[k], s, count, cost[k], dist);
+                            m = q[k] < m ? q[k] : m;
+                        }
+                        double sum = 0.0, wt = 0.0;
+                        for (int k = 0; k < 5; ++k) {
+                            if (!((legal >> k) & 1u)) continue;
+                            const double w = exp(beta * (m - q[k]));
+                            sum += w;
+                            if (k == tk) wt = w;
+                        }
+                        L[f * N + i] = wt / sum;
+                    }
+                }
+                if (raised) {
+                    fl |= kTbelfRaised;
+                } else {
+                    // 6. multiply
+                    fl |= kTbelfUpdated;
+                    for (int i = 0; i < N; ++i)
+                        for (int j = 0; j < N; ++j) {
+                            if (!is_live(i, j)) continue;
+                            const double l = i == j ? 2.0 * L[2 * N + i] : L[i] + L[N + j];
+                            belief[(i * N + j) * P] = belief[(i * N + j) * P] * l;
+                        }
+                    if (lik != nullptr) {
+                        for (int i = 0; i < 2 * N; ++i) lik[i * P] = L[i];
+                        for (int i = 0; i < S; ++i) lik[(2 * N + i) * P] = L[2 * N + i];
+                    }
+                }
+            }
+        }
+        // 7. normalise, and 8. the first maximum, both in reference order: the joints, then the splits
+        int key = -1;
+        if (normalise) {
+            double total = 0.0;
+            for (int t = 0; t < S; ++t)
+                if ((lJ >> t) & 1u) total += belief[(t * N + t) * P];
+            for (int i = 0; i < N; ++i)
+                for (int j = 0; j < N; ++j)
+                    if (i != j && is_live(i, j)) total += belief[(i * N + j) * P];
+            const double r = total == 0.0 ? 1.0 / (double)team_live_count(l0, l1, lJ) : 1.0 / total;
+            double bv = -1.0;
+            for (int pass = 0; pass < 2; ++pass)
+                for (int i = 0; i < N; ++i)
+                    for (int j = pass == 0 ? i : 0; j < (pass == 0 ? i + 1 : N); ++j) {
+                        if ((pass == 1 && i == j) || !is_live(i, j)) continue;
+                        double& b = belief[(i * N + j) * P];
+                        b = total == 0.0 ? r : b * r;
+                        if (b > bv) {
+                            bv = b;
+                            key = pass == 0 ? i : S + i * N + j;
+                        }
+                    }
+        }
+        int c0, c1, cJ;
+        team_map_bytes(key, S, c0, c1, cJ);
+        if (cJ < S) fl |= kTbelfJoint;
+        for (int c = 0; c < EP; ++c) {
+            ts[c * P] = (uint8_t)(open >> (8 * c));
+            ts[(EP + 2 * HP + c) * P] = (uint8_t)(lJ >> (8 * c));
+        }
+        for (int c = 0; c < HP; ++c) {
+            ts[(EP + c) * P] = (uint8_t)(l0 >> (8 * c));
+            ts[(EP + HP + c) * P] = (uint8_t)(l1 >> (8 * c));
+        }
+        if (map != nullptr) {
+            map[0] = (uint8_t)c0;
+            map[P] = (uint8_t)c1;
+            map[2 * P] = (uint8_t)cJ;
+        }
         if (info != nullptr) *info = (uint8_t)fl;
     }
 };

@@ -41,11 +41,17 @@ EXPORTED_SYMBOLS = (
     "oc_set_start_cells", "oc_get_start_cells", "oc_reset_random", "oc_cpu_reset_random",
     "oc_nav_policy", "oc_cpu_nav_policy", "oc_task_select", "oc_cpu_task_select",
     "oc_belief_update", "oc_cpu_belief_update", "oc_team_select", "oc_cpu_team_select",
+    "oc_team_belief_update", "oc_cpu_team_belief_update",
 )
 
 # oc_belief_update: the call flag, and the per-(env, watched agent) info bits
 OC_BELIEF_INIT = 1
 BELF_UPDATED, BELF_PRUNED, BELF_REINIT, BELF_RESET, BELF_RAISED = 0x01, 0x02, 0x04, 0x08, 0x10
+
+# oc_team_belief_update: the call flag, and the per-env info bits
+OC_TBELIEF_INIT = 1
+TBELF_UPDATED, TBELF_PRUNED, TBELF_REINIT, TBELF_RESET, TBELF_RAISED, TBELF_EMPTY, TBELF_JOINT = (
+    0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40)
 
 # oc_task_select: call flags, and the per-agent info bits
 OC_TASK_INIT, OC_TASK_COMMIT, OC_TASK_DISTINCT = 1, 2, 4
@@ -99,6 +105,24 @@ def belief_planes(S: int) -> int:
     S + 1 hypotheses (bit b of plane c is hypothesis 8c + b, hypothesis S is None).  A watched
     agent's bstate is 2 * HP planes (open, then live)."""
     return (S + 8) // 8
+
+
+def team_belief_planes(S: int) -> int:
+    """Byte planes of a pair's oc_team_belief_update state for S subtasks (OC_TBELIEF_PLANES): open
+    (event_planes(S) planes over the subtasks), live0 and live1 (belief_planes(S) planes each, over
+    0 .. S with S = None), liveJ (event_planes(S) planes)."""
+    return 2 * event_planes(S) + 2 * belief_planes(S)
+
+
+def team_belief_sets(tbstate, S: int):
+    """(open, live0, live1, liveJ) plane ranges of a [team_belief_planes(S), pitch] state."""
+    EP, HP = event_planes(S), belief_planes(S)
+    return tbstate[:EP], tbstate[EP:EP + HP], tbstate[EP + HP:EP + 2 * HP], tbstate[EP + 2 * HP:2 * EP + 2 * HP]
+
+
+def team_lik_planes(S: int) -> int:
+    """f64 planes of oc_team_belief_update's `lik`: L0 (S + 1), L1 (S + 1), LJ (S)."""
+    return 3 * S + 2
 
 
 class OcLevelDesc(ctypes.Structure):
@@ -333,6 +357,13 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.oc_team_select.argtypes = [vp, vp, vp, ctypes.POINTER(OcSubtask), i32, vp, i32, vp, vp, vp, i64, vp]
     lib.oc_cpu_team_select.restype = ctypes.c_int
     lib.oc_cpu_team_select.argtypes = [vp, vp, vp, ctypes.POINTER(OcSubtask), i32, vp, i32, vp, vp, vp, i64, i32]
+    dbl = ctypes.c_double
+    lib.oc_team_belief_update.restype = ctypes.c_int
+    lib.oc_team_belief_update.argtypes = [vp, vp, vp, vp, ctypes.POINTER(OcSubtask), i32, vp, i32, dbl, dbl, i32,
+                                          vp, vp, vp, vp, vp, i64, vp]
+    lib.oc_cpu_team_belief_update.restype = ctypes.c_int
+    lib.oc_cpu_team_belief_update.argtypes = [vp, vp, vp, vp, ctypes.POINTER(OcSubtask), i32, vp, i32, dbl, dbl, i32,
+                                              vp, vp, vp, vp, vp, i64, i32]
     lib.oc_belief_update.restype = ctypes.c_int
     lib.oc_belief_update.argtypes = [vp, vp, vp, vp, ctypes.POINTER(OcSubtask), i32, vp, i32, ctypes.c_double,
                                      ctypes.c_double, i32, vp, vp, vp, vp, i64, vp]

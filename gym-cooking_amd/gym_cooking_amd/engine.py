@@ -458,6 +458,66 @@ class OvercookedBatch(_StartCells):
                 self._stream())
         return _bound(self.lib.oc_belief_update, args)
 
+    def new_team_belief_state(self, S: int, lik: bool = True):
+        """Buffers of oc_team_belief_update for one pair over S subtasks, zeroed: (belief f64
+        [(S + 1)^2, pitch], tbstate u8 [capi.team_belief_planes(S), pitch], lik f64 [3 S + 2, pitch]
+        (None with lik=False: the call takes NULL there), map u8 [3, pitch], info u8 [pitch]).  The
+        first call on them passes capi.OC_TBELIEF_INIT.  The belief matrix costs (S + 1)^2 * 8 bytes
+        per env (839 MB at S = 9 and 2^20 envs)."""
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.device)  # noqa: E731
+        return (z(((S + 1) * (S + 1), self.pitch), torch.float64),
+                z((capi.team_belief_planes(S), self.pitch), torch.uint8),
+                z((capi.team_lik_planes(S), self.pitch), torch.float64) if lik else None,
+                z((3, self.pitch), torch.uint8), z((self.pitch,), torch.uint8))
+
+    def team_belief_update(self, prev: Optional[torch.Tensor], taken: Optional[torch.Tensor], subtasks, pair,
+                           self_agent: int, belief: torch.Tensor, tbstate: torch.Tensor,
+                           events: Optional[torch.Tensor] = None, beta: float = 1.3, none_action_prob: float = 0.5,
+                           flags: int = 0, lik: Optional[torch.Tensor] = None, map: Optional[torch.Tensor] = None,
+                           info: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The posterior over the allocation of `pair` = (a0, a1), a0 < a1, as the delegator
+        `self_agent` (one of the pair) infers it (oc_team_belief_update), updated in place over one
+        step: `prev`, `taken`, `events` as belief_update.  With N = S + 1, plane i * N + j of `belief`
+        is the split "a0 on i, a1 on j" (index S = None) for i != j and the joint "both on i" for
+        i == j < S.  `map` u8 [3, pitch] gets the most likely allocation as team_select's (cur0, cur1,
+        curJ): nav_policy's `alloc` planes.  `lik` f64 [3 S + 2, pitch] gets the step's likelihoods.
+        capi.OC_TBELIEF_INIT in `flags` starts every env over; the envs whose `prev` flags carry DONE
+        start over by themselves.  Not idempotent.  Returns info u8 [pitch] (capi.TBELF_*)."""
+        if info is None:
+            info = torch.empty(self.pitch, dtype=torch.uint8, device=self.device)
+        self.team_belief_update_launcher(prev, taken, subtasks, pair, self_agent, belief, tbstate, events, beta,
+                                         none_action_prob, flags, lik, map, info)()
+        return info
+
+    def team_belief_update_launcher(self, prev: Optional[torch.Tensor], taken: Optional[torch.Tensor], subtasks, pair,
+                                    self_agent: int, belief: torch.Tensor, tbstate: torch.Tensor,
+                                    events: Optional[torch.Tensor], beta: float, none_action_prob: float, flags: int,
+                                    lik: Optional[torch.Tensor], map: Optional[torch.Tensor],
+                                    info: Optional[torch.Tensor]):
+        """An oc_team_belief_update call bound once (see rollout_launcher)."""
+        S = len(subtasks)
+        if len(pair) != 2:
+            raise ValueError("team_belief_update: a pair of agents, got %r" % (tuple(pair),))
+        if prev is not None:
+            self._check(prev, self.layout.state_bytes)
+        if taken is not None:
+            self._check(taken, self.A * self.pitch)
+        if events is not None:
+            self._check(events, capi.event_planes(S) * self.pitch)
+        self._check(belief, 8 * (S + 1) * (S + 1) * self.pitch, (torch.float64,))
+        self._check(tbstate, capi.team_belief_planes(S) * self.pitch)
+        if lik is not None:
+            self._check(lik, 8 * capi.team_lik_planes(S) * self.pitch, (torch.float64,))
+        if map is not None:
+            self._check(map, 3 * self.pitch)
+        if info is not None:
+            self._check(info, self.pitch)
+        ags = (ctypes.c_uint8 * 2)(*[int(a) for a in pair])
+        args = (self._h, _ptr(prev), _ptr(taken), _ptr(events), capi.subtask_array(subtasks), S, ags, int(self_agent),
+                float(beta), float(none_action_prob), int(flags), _ptr(belief), _ptr(tbstate), _ptr(lik), _ptr(map),
+                _ptr(info), self.B, self._stream())
+        return _bound(self.lib.oc_team_belief_update, args)
+
     def subtask_bounds(self, state: torch.Tensor, subtasks, lower_bound: Optional[torch.Tensor] = None,
                        doable: Optional[torch.Tensor] = None):
         """Full-state subtask bounds (oc_subtask_bounds): for every env and configuration,
@@ -782,6 +842,41 @@ class CpuStepper(_StartCells):
         capi.check(self.lib.oc_cpu_belief_update(self._h, p(prev), p(taken), p(events), capi.subtask_array(subtasks), S,
                                                  ags, M, float(beta), float(none_action_prob), int(flags), p(belief),
                                                  p(bstate), p(map), p(info), B, self.nthreads))
+        return info
+
+    def new_team_belief_state(self, S: int):
+        """Host buffers of oc_cpu_team_belief_update, zeroed; mirrors OvercookedBatch.new_team_belief_state."""
+        P = self.pitch
+        return (np.zeros(((S + 1) * (S + 1), P), np.float64), np.zeros((capi.team_belief_planes(S), P), np.uint8),
+                np.zeros((capi.team_lik_planes(S), P), np.float64), np.zeros((3, P), np.uint8), np.zeros(P, np.uint8))
+
+    def team_belief_update(self, prev: Optional[np.ndarray], taken: Optional[np.ndarray], subtasks, pair,
+                           self_agent: int, belief: np.ndarray, tbstate: np.ndarray,
+                           events: Optional[np.ndarray] = None, beta: float = 1.3, none_action_prob: float = 0.5,
+                           flags: int = 0, lik: Optional[np.ndarray] = None, map: Optional[np.ndarray] = None,
+                           info: Optional[np.ndarray] = None) -> np.ndarray:
+        """oc_cpu_team_belief_update: the posterior over the pair's allocation in the host buffers;
+        mirrors OvercookedBatch.team_belief_update.  `belief` f64 [(S + 1)^2, pitch] and `tbstate` u8
+        [capi.team_belief_planes(S), pitch] are updated in place; only columns below B are written
+        (buffers may end at column B of their last plane).  Returns info u8 [pitch]."""
+        S, B, P = len(subtasks), self.B, self.pitch
+        if len(pair) != 2:
+            raise ValueError("team_belief_update: a pair of agents, got %r" % (tuple(pair),))
+        info = np.zeros(P, np.uint8) if info is None else info
+        for a, n, dt in ((prev, self.layout.state_bytes, np.uint8), (taken, (self.A - 1) * P + B, np.uint8),
+                         (events, (capi.event_planes(S) - 1) * P + B, np.uint8),
+                         (belief, 8 * (((S + 1) * (S + 1) - 1) * P + B), np.float64),
+                         (tbstate, (capi.team_belief_planes(S) - 1) * P + B, np.uint8),
+                         (lik, 8 * ((capi.team_lik_planes(S) - 1) * P + B), np.float64),
+                         (map, 2 * P + B, np.uint8), (info, B, np.uint8)):
+            if a is not None and (a.dtype != dt or not a.flags.c_contiguous or a.nbytes < n):
+                raise ValueError("host buffers: contiguous %s of at least %d bytes" % (np.dtype(dt), n))
+        p = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        ags = (ctypes.c_uint8 * 2)(*[int(a) for a in pair])
+        capi.check(self.lib.oc_cpu_team_belief_update(self._h, p(prev), p(taken), p(events),
+                                                      capi.subtask_array(subtasks), S, ags, int(self_agent), float(beta),
+                                                      float(none_action_prob), int(flags), p(belief), p(tbstate),
+                                                      p(lik), p(map), p(info), B, self.nthreads))
         return info
 
     def progress(self, state_prev: np.ndarray, states: np.ndarray, subtasks, weights=None, n: int = 1,

@@ -846,6 +846,7 @@ class OvercookedVecEnv:
         self._task_round = None  # partner_tasks(): the next call starts every env over
         self._belief_round = None  # partner_beliefs(): likewise
         self._team_round = None  # team_tasks(): likewise
+        self._tbelief_round = None  # team_beliefs(): likewise
         return self.state
 
     def step(self, actions: torch.Tensor):
@@ -1080,6 +1081,86 @@ class OvercookedVecEnv:
         for q, (table, ncand) in enumerate(zip(tables[pair], (5, 5, 25))):
             self.batch.nav_policy(self.state, table, out, beta=beta, mode=mode, alloc=self._team[EP + q], step=self._round,
                                   seed=self.seed, num_cand=ncand, flags=self.team_flags[q])
+        return out.view(self.A, self.P)[:, :self.num_envs], info
+
+    def team_beliefs(self, pair, self_agent: int, beta: float = 1.3, none_action_prob: float = 0.5,
+                     use_events: bool = True):
+        """What the pair `pair` = (a0, a1), a0 < a1, is doing together, as the delegator `self_agent`
+        (a0 or a1) infers it from what both did (oc_team_belief_update over ``subtasks``): per env
+        the reference's Bayesian Delegation posterior over "both on subtask t" and "a0 on i, a1 on
+        j" (None allowed for one member), updated over the last step() with both executed actions.
+        partner_beliefs' life cycle: the first call after reset() (or with another pair or self
+        agent) initialises every env, a call after a step updates over that step (only the last one:
+        call once per step) and starts over the envs it auto-reset, and a second call on the same
+        states changes nothing.  Opt-in: step() does not compute it; the matrix costs
+        (S + 1)^2 * 8 bytes per env.  Returns (belief f64 [N, N, B] with N = S + 1: entry (i, j) the
+        split for i != j, the joint for i == j < S, index S None, (S, S) unused; cur0, cur1, curJ u8
+        [B], the most likely allocation in team_tasks' format; info u8 [B] of capi.TBELF_*), views of
+        this env's buffers."""
+        pair = tuple(int(a) for a in pair)
+        S = len(self.subtasks)
+        if S == 0:
+            raise ValueError("the level's recipes have no subtasks")
+        B, N = self.num_envs, S + 1
+        key = (pair, int(self_agent))
+        if getattr(self, "_tbelief_key", None) != key:
+            self._tbelief_key = key
+            self._tbelief = self.batch.new_team_belief_state(S, lik=False)  # the likelihoods are not kept here
+            self._tbelief_events = torch.zeros((1, capi.event_planes(S), self.P), dtype=torch.uint8,
+                                               device=self.batch.device)
+            self._tbelief_round = None
+        bel, tbs, _, tmap, info = self._tbelief
+        if getattr(self, "_tbelief_round", None) is None:
+            self.batch.team_belief_update(None, None, self._sub_rows, pair, self_agent, bel, tbs, None, beta,
+                                          none_action_prob, capi.OC_TBELIEF_INIT, None, tmap, info)
+        elif self._tbelief_round != self._round:  # stepped since: the other buffer is the state before
+            prev, events = self._s[self._i ^ 1], None
+            if use_events:
+                events = self._tbelief_events
+                self.batch.progress(prev, self.state, self._sub_rows, None, 1, None, events, None)
+            self.batch.team_belief_update(prev, self.ex, self._sub_rows, pair, self_agent, bel, tbs, events, beta,
+                                          none_action_prob, 0, None, tmap, info)
+        self._tbelief_round = self._round
+        return bel.view(N, N, self.P)[:, :, :B], tmap[0, :B], tmap[1, :B], tmap[2, :B], info[:B]
+
+    def delegate_actions(self, self_agent: int, other: int, beta: float = 1.3,
+                         mode: int = capi.OC_POLICY_SAMPLE | capi.OC_POLICY_COUNT_STATE,
+                         out: Optional[torch.Tensor] = None, none_action_prob: float = 0.5, use_events: bool = True):
+        """Actions of a Bayesian-delegation partner `self_agent` beside the agent `other` (a learner,
+        say): team_beliefs infers the pair's allocation from what both did, and the partner plays its
+        own member of the most likely one.  Two oc_nav_policy launches: self's one-agent table (the
+        level's subtasks, then None) with self's cur plane as `alloc` writes into `out`; the
+        two-agent table with plane curJ writes into a private scratch buffer, and self's row of it
+        is copied into `out` where the allocation is joint.  Only self's bytes of `out` (u8 [A,
+        pitch]; None: this env's buffer) are ever written: the other agent's survive.
+        Returns (the [A, B] view of `out`, belief info u8 [B])."""
+        me, other = int(self_agent), int(other)
+        if me == other:
+            raise ValueError("delegate_actions: self_agent and other are one agent")
+        pair = (min(me, other), max(me, other))
+        _, cur0, cur1, curJ, info = self.team_beliefs(pair, me, beta, none_action_prob, use_events)
+        if out is None:
+            if getattr(self, "_partner", None) is None:
+                self._partner = self.batch.new_actions()
+            out = self._partner
+        if getattr(self, "_delegate_scratch", None) is None:
+            self._delegate_scratch = self.batch.new_actions()
+            self.delegate_flags = torch.zeros((2, self.P), dtype=torch.uint8, device=self.batch.device)
+        tables = self.__dict__.setdefault("_delegate_tables", {})
+        if (me, other) not in tables:
+            enc = self.batch.level.encoding
+            tables[(me, other)] = (capi.policy_subtasks(list(self.subtasks) + [None], enc, [me]),
+                                   capi.policy_subtasks(list(self.subtasks), enc, pair))
+        own, joint = tables[(me, other)]
+        tmap = self._tbelief[3]
+        S = len(self.subtasks)
+        self.batch.nav_policy(self.state, own, out, beta=beta, mode=mode, alloc=tmap[0 if me == pair[0] else 1],
+                              step=self._round, seed=self.seed, num_cand=5, flags=self.delegate_flags[0])
+        self.batch.nav_policy(self.state, joint, self._delegate_scratch, beta=beta, mode=mode, alloc=tmap[2],
+                              step=self._round, seed=self.seed, num_cand=25, flags=self.delegate_flags[1])
+        B = self.num_envs
+        mine, theirs = out.view(self.A, self.P)[me, :B], self._delegate_scratch.view(self.A, self.P)[me, :B]
+        torch.where(tmap[2, :B] < S, theirs, mine, out=mine)
         return out.view(self.A, self.P)[:, :self.num_envs], info
 
     def episode_stats(self) -> torch.Tensor:

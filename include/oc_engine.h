@@ -979,6 +979,131 @@ int oc_cpu_belief_update(const oc_handle* h, const void* state_prev, const uint8
                          double beta, double none_action_prob, int32_t flags, double* belief, uint8_t* bstate,
                          uint8_t* map, uint8_t* info, int64_t B, int32_t nthreads);
 
+/* ---------------------------------------------------------------------------------------
+ * Per-env Bayesian belief over a pair's allocation (additive to ABI 12): Bayesian Delegation itself
+ * (model `bd`) on the batch.  oc_belief_update reasons about "agent a alone follows subtask i"; this
+ * call keeps the reference delegator's posterior over the whole allocation space of two agents,
+ * "both on t" beside "a0 on i, a1 on j", updates it with the actions both agents executed, and maps
+ * it to the three `alloc` planes of oc_team_select's format: the delegator then acts on its own
+ * member of the most likely allocation.
+ *   add_subtasks (the enumeration and its order)    delegation_planner/bayesian_delegator.py:697-886
+ *   prune_subtask_allocs, subtask_alloc_is_doable   bayesian_delegator.py:200-256, :98-156
+ *   bayes_update                                    bayesian_delegator.py:1026-1072
+ *   prob_nav_actions (no_level_1)                   bayesian_delegator.py:461-689
+ *   select_subtask                                  bayesian_delegator.py:1009-1017
+ *   update_subtasks (set_priors after a completion) gym_cooking/utils/agent.py:176-203
+ *   normalize, get_max                              delegation_planner/utils.py:186-215
+ * Build-defined, and only these: uniform priors (the reference also offers spatial priors); the
+ * likelihoods of a fresh planner configured on obs_tm1 with no_level_1 = True (oc_nav_policy's Q
+ * values, not BRTDP-updated ones); ties of the maximum go to the first hypothesis in reference order
+ * (get_max draws at random); and a None member whose self agent has no movable action (n = 0, where
+ * the reference divides by zero) has likelihood 1 for the no-op and 0 otherwise.
+ *
+ * The pair is a0 = agents[0] < a1 = agents[1]; self_agent, the delegator, is a0 or a1.  With S =
+ * num_subtasks, N = S + 1, EP = OC_PROGRESS_EVENT_PLANES(S) and HP = OC_BELIEF_PLANES(S), the
+ * hypotheses form an N x N matrix, hypothesis (i, j) in plane i * N + j of `belief`:
+ *   i != j     the split "a0 alone on subtask i, a1 alone on subtask j", index S meaning None
+ *   i == j < S the joint "both on subtask i"
+ *   (S, S)     no hypothesis: the plane is never read or written
+ * Reference order is add_subtasks' order for two agents: the joints by ascending i, then the splits
+ * in row-major (i, j).  OC_SUB_NONE rows inside the table are never hypotheses.
+ * The state of an env is u8 [OC_TBELIEF_PLANES(S) = 2 EP + 2 HP][pitch], four bit sets in
+ * oc_belief_update's numbering (bit b of plane c is index 8c + b):
+ *   planes 0 .. EP-1          open : the subtasks nobody has completed this episode
+ *   EP .. EP+HP-1             live0: a0's members still in the distribution, over 0 .. S
+ *   EP+HP .. EP+2HP-1         live1: a1's
+ *   EP+2HP .. 2EP+2HP-1       liveJ: the joint members
+ * A split (i, j) is live iff live0 has i and live1 has j; a joint i iff liveJ has i.  The factored
+ * form is exact: the reference deletes an allocation iff one of its members is not doable
+ * (bayesian_delegator.py:1031-1038), and that is decided per member.  n_live counts the live
+ * hypotheses.  The rule, for env e:
+ *   1. initialise, with OC_TBELIEF_INIT or when state_prev's flags carry OC_FLAG_DONE: open = the
+ *      rows whose kind is not OC_SUB_NONE; live0 = live1 = open plus bit S; liveJ = open; every live
+ *      belief = 1.0 / n_live, every other plane of the matrix +0.0.  OC_TBELF_REINIT; go to 7.
+ *   2. reset priors, if events is given and events & open is non-zero (agent.py:185-192): open &=
+ *      ~events; the live sets from open and the beliefs uniform as in 1.  OC_TBELF_RESET; go to 7.
+ *   3. prune: live0 loses i < S if the row {kind_i, 1 agent {a0}, masks_i} is not doable on
+ *      state_prev (exactly oc_subtask_bounds' doable byte); live1 loses j likewise with {a1}; liveJ
+ *      loses t likewise with {a0, a1}.  The belief of every hypothesis that left becomes +0.0, and
+ *      OC_TBELF_PRUNED is set if one did.
+ *   4. empty: if n_live is 0, OC_TBELF_EMPTY; go to 8 (the reference has nobody on anything).
+ *   5. raise test.  The members form three families: a0's one-agent rows, a1's, and the pair's
+ *      two-agent rows.  A family raises where oc_nav_likelihood would flag its rows OC_LIK_RAISES:
+ *      its Level-0 configuration raises, the taken action (the pair's: the taken joint action) is not
+ *      in get_actions on its Level-0 view, or a legal candidate's transition ends with the pair on
+ *      one square.  None of these reads the subtask: interact, the legality tests and the removed
+ *      agents depend on the family's agents only, for the two-agent rows as for the one-agent rows,
+ *      so the test is made once per family.  If a family raises that has a subtask (not None) as
+ *      a member of some live hypothesis: OC_TBELF_RAISED, and step 6 is skipped.
+ *   6. multiply (one f64 add and one f64 multiply per live hypothesis; bayes_update's factor is the
+ *      sum over the members of len(agents) * prob_nav_actions):
+ *        split (i, j): belief = belief * (L0_i + L1_j);   joint t: belief = belief * (2.0 * LJ_t)
+ *      Each L is oc_nav_likelihood's value for (state_prev, taken, the member's row, self_agent,
+ *      beta, none_action_prob) with the goal count of state_prev's own Level-0 view
+ *      (OC_POLICY_COUNT_STATE): over the legal candidates k, m = min Q_k, w_k = exp(beta * (m -
+ *      Q_k)), the sum ascending from +0.0, L = w_taken / sum.  A one-agent row has the member's five
+ *      actions as candidates.  For a joint row self is inside the pair, so the candidates are the
+ *      five joint actions that keep the other member's taken action (:676-680), not 25.  For None,
+ *      n is the *self* agent's movable actions in the full state (:621; the reference's quirk, and
+ *      unlike oc_belief_update) while the tested action is the member's: oc_nav_policy's closed
+ *      form, p(no-op) if the member's taken action is the no-op, else p(each movable action).
+ *      OC_TBELF_UPDATED.
+ *   7. normalise (utils.py:186-193): total = +0.0 plus the live beliefs in reference order; if total
+ *      is 0 every live belief = 1.0 / n_live, else each is multiplied by 1.0 / total.  That order
+ *      is the host call's.  The device call adds each lane's hypotheses (row-major, columns j = lane
+ *      mod 8) and then the 8 lanes' sums pairwise, so its total, and every belief with it, can
+ *      differ from the host's in the last bits: the two are tested to agree to 1e-12.
+ *   8. map = the first hypothesis in reference order holding the maximum, as oc_team_select's
+ *      (cur0, cur1, curJ): a joint t is (OC_TEAM_OUT, OC_TEAM_OUT, t), a split (i, j) is
+ *      (i, j, OC_TEAM_OUT), nothing live is the idle split (S, S, OC_TEAM_OUT).  The three planes are
+ *      directly the `alloc` planes of three oc_nav_policy launches.  OC_TBELF_JOINT iff it is joint.
+ * A second call without a step in between is not idempotent: it multiplies again.
+ * Memory: the belief matrix is (S + 1)^2 * 8 bytes per env, 839 MB at S = 9 and 2^20 envs.
+ * ------------------------------------------------------------------------------------- */
+#define OC_TBELIEF_INIT 1         /* every env below B starts its episode: step 1 for all of them */
+#define OC_TBELF_UPDATED 0x01     /* step 6 ran */
+#define OC_TBELF_PRUNED  0x02     /* a hypothesis left the distribution in step 3 */
+#define OC_TBELF_REINIT  0x04     /* initialised in this call (step 1) */
+#define OC_TBELF_RESET   0x08     /* uniform priors over the open subtasks after a completion (step 2) */
+#define OC_TBELF_RAISED  0x10     /* the reference's likelihood raises: pruned and normalised only */
+#define OC_TBELF_EMPTY   0x20     /* step 3 left no hypothesis (step 4) */
+#define OC_TBELF_JOINT   0x40     /* the map is a joint allocation */
+#define OC_TBELIEF_PLANES(S) (2 * OC_PROGRESS_EVENT_PLANES(S) + 2 * OC_BELIEF_PLANES(S))
+
+/*   state_prev, taken, events : as oc_belief_update (with OC_TBELIEF_INIT all three may be NULL)
+ *   subtasks     : host array of S = num_subtasks rows, 1 <= S <= OC_TEAM_MAX_SUBTASKS; only kind,
+ *                  start_mask and goal_mask are read
+ *   agents       : host array of 2 agent indices, a0 < a1 < A (so A >= 2)
+ *   self_agent   : the delegator, a0 or a1
+ *   beta, none_action_prob : as oc_nav_policy (none_action_prob in [0, 1])
+ *   belief       : required, f64 [N * N][pitch], 8-byte aligned, read and written in place
+ *   tbstate      : required, u8 [OC_TBELIEF_PLANES(S)][pitch], read and written in place
+ *   lik          : nullable, f64 [3 S + 2][pitch], 8-byte aligned: the step's L0 (planes 0 .. S),
+ *                  L1 (N .. N + S) and LJ (2 N .. 2 N + S - 1), written where step 6 ran: +0.0 for a
+ *                  member outside its live set or whose family raises
+ *   map          : nullable, u8 [3][pitch]: cur0, cur1, curJ
+ *   info         : nullable, u8 [pitch], OC_TBELF_* bits
+ * Columns >= B of every buffer stay untouched; a belief plane is written only where step 1 or 2 ran
+ * or the hypothesis was live at entry.  Stream-ordered, no allocation, no synchronisation
+ * (hipGraph-capturable, as oc_step).  Bad arguments, A = 1 and a host-only handle are OC_EINVAL;
+ * B = 0 is OK. */
+int oc_team_belief_update(const oc_handle* h, const void* state_prev, const uint8_t* taken, const uint8_t* events,
+                          const oc_subtask* subtasks, int32_t num_subtasks, const uint8_t* agents, int32_t self_agent,
+                          double beta, double none_action_prob, int32_t flags, double* belief, uint8_t* tbstate,
+                          double* lik, uint8_t* map, uint8_t* info, int64_t B, void* stream);
+
+/* The same on the host (what oc_cpu_step is to oc_step): HOST buffers, works on OC_DEVICE_HOST
+ * handles, the whole rule per env as one scalar row function, threaded over env ranges (nthreads
+ * 0 = the host's hardware threads; at least 1,024 rows each).  It never touches the device;
+ * oc_team_belief_update never calls it.  The two agree on tbstate and info byte for byte and, up to
+ * the last bits of exp, of a fused multiply-add and of the order of step 7's sum (the device adds
+ * per lane, then across lanes), on belief and lik; map, and with it OC_TBELF_JOINT, is each call's
+ * first maximum of its own beliefs (L0_i + L1_j and 2 LJ_t can be one ulp apart). */
+int oc_cpu_team_belief_update(const oc_handle* h, const void* state_prev, const uint8_t* taken, const uint8_t* events,
+                              const oc_subtask* subtasks, int32_t num_subtasks, const uint8_t* agents,
+                              int32_t self_agent, double beta, double none_action_prob, int32_t flags, double* belief,
+                              uint8_t* tbstate, double* lik, uint8_t* map, uint8_t* info, int64_t B, int32_t nthreads);
+
 #ifdef __cplusplus
 }
 #endif
